@@ -1,8 +1,16 @@
 """Benchmark: FCE-YOLOv11 detection inference (forward + decode + NMS) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model yolo11n-fce.yaml] [--batch 32] [--imgsz 640]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline `value` and
+`ms_per_step` with the run's configuration).  `--dump-outputs DIR` also writes what the last timed step computed
+(the detections a caller of the timed path receives) as DIR/<name>.npy: the inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.  `--full` adds every other leg to the line:
+the forward-only and one-batch-at-a-time timings, the per-op profile with its roofline figures, the one-rank
+process-group configuration, the host-image predict path and the CPU baseline (each with its own switch below).
 
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) launches the N ranks itself: before
 torch is even imported, it runs the torch.distributed.run command above as a child process (one rank per
@@ -156,6 +164,13 @@ def parse_args():
     ap.add_argument("--graph", type=int, default=-1, help="1: replay a captured hipGraph per lane; 0: direct "
                     "launches; -1 (default): replay when lanes > 1 (ties direct launches there, 28.2k both; with one "
                     "lane direct launches are faster, DESIGN.md)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (rank 0: the whole global batch) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: forward-only and one-lane timings, per-op "
+                         "profile and roofline, `value_dist_config`, the host-image predict path, the CPU baseline "
+                         "(the options below choose among them and act only with --full)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--profile-json", default=None, help="write the per-op profile here")
     ap.add_argument("--profile-passes", type=int, default=10, help="per-op HIP-event passes averaged")
@@ -177,6 +192,10 @@ def parse_args():
                          "forward, NMS, scale_boxes, per-batch gather of the detections) -- PCIe inclusive, not `value` "
                          "of the contract line")
     a = ap.parse_args()
+    if a.profile_json and not a.full:
+        ap.error("--profile-json needs --full (the per-op profile is one of its legs)")
+    if a.dump_outputs and a.source == "host":
+        ap.error("--dump-outputs writes the outputs of the resident-input path (--source device)")
     a.lanes_given = a.lanes
     if a.lanes is None:
         a.lanes = default_lanes(a.model, os.environ, a.gpus)
@@ -295,8 +314,7 @@ def dist_config_line(a):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", f"--master-port={port}", str(Path(__file__).resolve()), "--gpus", "1",
            "--steps", str(a.dist_config_steps), "--warmup", str(a.warmup), "--model", a.model, "--batch", str(a.batch),
-           "--imgsz", str(a.imgsz), "--cpu-seconds", "0", "--predict-steps", "0", "--profile-passes", "1",
-           "--dist-config-steps", "0"]
+           "--imgsz", str(a.imgsz)]  # a plain run: the child times its steps and prints the line
     if a.lanes_given is not None:  # an explicit --lanes is what the --gpus N ranks would run too
         cmd += ["--lanes", str(a.lanes_given)]
     try:
@@ -369,6 +387,47 @@ def host_source_line(a, model, rank, world, use_dist, dev):
     }
 
 
+DUMP_MAX_BYTES = 16 << 20  # per dumped array (three at the most)
+
+
+def last_outputs(a, sp, eng, nms, slot):
+    """What a caller of the timed path holds after the last step, as host float arrays: the forward's prediction
+    (--no-nms), else the NMS results of the whole global batch in image order -- `dets` (images, max_det, 6) rows
+    [x1, y1, x2, y2, conf, cls], `keep` (images, max_det) kept anchor indices and `counts` (images,); the rows past
+    an image's count are 0 in `dets` and -1 in `keep`."""
+    import numpy as np
+
+    if a.no_nms:
+        torch.cuda.synchronize()
+        return {"pred": eng.pred.cpu().numpy()}
+    dets, keep = nms.results() if a.sequential else sp.results(slot)
+    n, md = len(dets), nms.max_det
+    d, k, c = np.zeros((n, md, 6), np.float32), np.full((n, md), -1.0, np.float64), np.zeros(n, np.float64)
+    for i, (di, ki) in enumerate(zip(dets, keep)):
+        c[i] = m = int(di.shape[0])
+        d[i, :m] = di.cpu().numpy()
+        k[i, :m] = ki.cpu().numpy()
+    return {"dets": d, "keep": k, "counts": c}
+
+
+def dump_outputs(path, arrays):
+    """Write each array as <path>/<name>.npy (float32 or float64).  An array above DUMP_MAX_BYTES is cut to a fixed
+    seeded sample of its elements: the same flat indices on every run, in index order."""
+    import numpy as np
+
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    info = {}
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        shape, cap = list(arr.shape), DUMP_MAX_BYTES // arr.itemsize
+        if arr.size > cap:
+            arr = arr.reshape(-1)[np.sort(np.random.default_rng(0).choice(arr.size, cap, replace=False))]
+        np.save(d / f"{name}.npy", arr)
+        info[name] = {"saved": list(arr.shape), "of": shape}
+    return {"dir": str(d), "arrays": info}
+
+
 def main():
     a = parse_args()
     rank = int(os.environ.get("RANK", 0))
@@ -423,6 +482,7 @@ def main():
     x = xs[0]
     nms = NMS(B, eng.anchors, eng.nc, dev)
     it = [0]
+    slot = [0]  # the pipeline slot of the last submitted batch (its results: --dump-outputs)
 
     def step():
         xi = xs[it[0] % len(xs)]
@@ -432,7 +492,7 @@ def main():
         elif a.sequential:
             nms(eng(xi), eng.best)
         else:  # forward of this batch overlaps the NMS (+ multi-GPU gather) of the previous one
-            sp.submit(xi)
+            slot[0] = sp.submit(xi)
 
     def barrier():
         if use_dist:
@@ -442,7 +502,8 @@ def main():
     for _ in range(a.warmup):
         step()
     sp.flush()
-    _trace_marker()
+    if a.full:
+        _trace_marker()
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -450,14 +511,53 @@ def main():
     sp.flush()  # the last batch's NMS (+ gather) is inside the timed region
     barrier()
     el = time.perf_counter() - t0
-    _trace_marker()
-    t = torch.tensor([el], dtype=torch.float64, device=dev)
-    if use_dist:
+    if a.full:
+        _trace_marker()
+    if use_dist:  # max over ranks
+        t = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    el = float(t.item())
+        el = float(t.item())
     ms_step = el / a.steps * 1e3
     total_imgs = world * B * a.steps
     value = total_imgs / el
+    stem = Path(a.model).stem
+    out = {
+        "metric": "images/sec/GPU @ 640x640 bs=32, yolo11n-fce; fraction of fp16 MFMA roofline",
+        "value": round(value, 2),
+        "unit": "images/sec",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp16",
+        "data": "synthetic torch.rand(B,3,S,S) fp16 per rank; seeded random-init weights of the architecture",
+        "config": {"workload": f"{stem} detection inference (forward + decode + NMS) @ {S}x{S}, {B} images/GPU",
+                   "model": stem, "global_batch": B * world, "imgsz": S, "parallelism": f"dp{world}",
+                   "batches_in_flight": 1 if (a.no_nms or a.sequential) else a.lanes,
+                   "distinct_inputs": len(xs),
+                   "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4),
+                   "forward_launch": "hipgraph" if a.graph else "direct"},
+    }
+    if a.dump_outputs and a.steps > 0 and rank == 0:
+        out["outputs"] = dump_outputs(a.dump_outputs, last_outputs(a, sp, eng, nms, slot[0]))
+
+    def finish():
+        out["process_group"] = ({"backend": dist.get_backend(), "world_size": dist.get_world_size()} if use_dist
+                                else None)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if sp is not None:
+            sp.close()
+
+    if not a.full:  # a plain run ends here; everything below is a leg of --full
+        finish()
+        return
 
     # forward-only time (graph replay) for reference
     barrier()
@@ -530,32 +630,13 @@ def main():
     roof["launches_per_step"] = dn
     roof["kernel_ms_per_step"] = round(dms, 4)
     kernel_ms = sum(p[3] for p in prof)
-    stem = Path(a.model).stem
     batch_flops = sum(p[2] for p in prof)  # 2*MAC of every conv / matmul of one batch (op_cost)
     batch_bytes = sum(p[1] for p in prof)  # algorithmic bytes of every op of one batch (op_cost)
     # whole-forward roofline: achieved = img/s x GFLOP/img against min(MFMA peak, AI x HBM peak)
     ai_fwd = batch_flops / max(batch_bytes, 1.0)
     roof_tfs = min(MFMA_F16_PEAK_TFS, ai_fwd * HBM_PEAK_GBS / 1e3)
     ach_tfs = value / world * batch_flops / B / 1e12
-    out = {
-        "metric": "images/sec/GPU @ 640x640 bs=32, yolo11n-fce; fraction of fp16 MFMA roofline",
-        "value": round(value, 2),
-        "unit": "images/sec",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "fp16",
-        "data": "synthetic torch.rand(B,3,S,S) fp16 per rank; seeded random-init weights of the architecture",
-        "config": {"workload": f"{stem} detection inference (forward + decode + NMS) @ {S}x{S}, {B} images/GPU",
-                   "model": stem, "global_batch": B * world, "imgsz": S, "parallelism": f"dp{world}",
-                   "batches_in_flight": 1 if (a.no_nms or a.sequential) else a.lanes,
-                   "distinct_inputs": len(xs),
-                   "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4),
-                   "forward_launch": "hipgraph" if a.graph else "direct"},
+    out.update({
         "roofline": roof,
         "roofline_forward": {"achieved": round(ach_tfs, 3), "peak": round(roof_tfs, 2), "unit": "TFLOP/s",
                              "frac": round(ach_tfs / roof_tfs, 4), "ai_flop_per_byte": round(ai_fwd, 2),
@@ -574,7 +655,7 @@ def main():
         "kernels": {k: {"ms": round(v[0], 4), "launches": v[3], "GB/s": round(v[1] / (v[0] * 1e-3) / 1e9, 1)
                         if v[0] else None, "TFLOP/s": round(v[2] / (v[0] * 1e-3) / 1e12, 2) if v[0] else None}
                     for k, v in sorted(fam.items(), key=lambda kv: -kv[1][0])},
-    }
+    })
     if a.profile_json and rank == 0:
         Path(a.profile_json).write_text(json.dumps([list(p) for p in prof], indent=0))
     if rank == 0 and world == 1 and (a.predict_steps > 0 or a.dist_config_steps > 0):
@@ -591,15 +672,7 @@ def main():
         out["cpu_baseline"] = cpu_baseline(a.model, S, a.cpu_seconds, B)
     elif rank == 0:
         out["cpu_baseline"] = None
-    out["process_group"] = ({"backend": dist.get_backend(), "world_size": dist.get_world_size()} if use_dist
-                            else None)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
-    if sp is not None:
-        sp.close()
+    finish()
 
 
 if __name__ == "__main__":

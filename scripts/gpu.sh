@@ -2,7 +2,7 @@
 # GPU run-tooling in one place (run on the box through gpurun, from the repo root).  Every GPU step runs
 # under its own time limit and the first failure (test failures aside) ends the call.
 #
-#   gpu.sh check TAG                  full -m gpu suite + smoke + the driver's plain `python bench.py`
+#   gpu.sh check TAG                  full -m gpu suite + smoke + `python bench.py --full` (every leg of the bench)
 #   gpu.sh quick TAG "<pytest -k>"    a -k selection of the GPU tests, then a 30-step bench
 #   gpu.sh bench TAG [bench args]     one bench line (no CPU baseline, no predict leg)
 #   gpu.sh env TAG "A=1 B=2" "A=0" .. one bench line per environment setting, interleaved twice (A/B runs)
@@ -32,7 +32,7 @@ pytest_gpu() {  # $1 log, rest: pytest args
 bench_line() {  # $1 log, rest: bench args
   local log=$1
   shift
-  timeout -k 10 400 python bench.py "$@" > "$log" 2>&1
+  timeout -k 10 400 python bench.py --full "$@" > "$log" 2>&1
   local rc=$?
   echo "bench rc=$rc $(grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*\|"forward_ms_per_batch": [0-9.]*\|"frac": [0-9.]*' "$log" | tr '\n' ' ')"
   return $rc
@@ -63,7 +63,7 @@ case "$CMD" in
       for setting in "$@"; do
         i=$((i + 1))
         echo -n "[$setting] "
-        env $setting timeout -k 10 300 python bench.py --steps 100 --warmup 10 --cpu-seconds 0 --predict-steps 0 --dist-config-steps 0 \
+        env $setting timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --cpu-seconds 0 --predict-steps 0 --dist-config-steps 0 \
           --profile-passes 3 $BARGS > "$OUT/env$i.log" 2>&1
         rc=$?
         echo "rc=$rc $(grep -o '"value": [0-9.]*\|"forward_ms_per_batch": [0-9.]*\|"value_1lane": [0-9.]*' "$OUT/env$i.log" | tr '\n' ' ')"

@@ -14,7 +14,7 @@ pass() {
     --profile-json gpurun_out/pmc/${TAG}_profile_$name.json $BARGS > gpurun_out/pmc/${TAG}_$name.log 2>&1
   local rc=$?; echo "pmc $name rc=$rc"; return $rc
 }
-BARGS="$*"
+BARGS="--full $*"  # the per-op profile pass is a leg of --full
 pass FETCH FETCH_SIZE && pass WRITE WRITE_SIZE && pass MFMA SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE || exit $?
 python scripts/pmc_summary.py gpurun_out/pmc/${TAG}_FETCH gpurun_out/pmc/${TAG}_WRITE gpurun_out/pmc/${TAG}_profile_FETCH.json gpurun_out/pmc/${TAG}_MFMA > gpurun_out/pmc/${TAG}_summary.json
 rc=$?; python -c "import json;d=json.load(open('gpurun_out/pmc/${TAG}_summary.json'))['families'];print({k:(round(v['hbm_over_alg'],2),v.get('mfma_frac')) for k,v in d.items()})"

@@ -7,6 +7,7 @@ export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-8}  # the bench default (4 lanes) asks for 8; set before rocprofv3 starts the program
 TAG=${1:-r01}
 shift
+set -- --full "$@"  # the trace markers and the per-kernel figures the summary is set beside
 STEPS=20
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/$TAG -o run -- \
   python bench.py --steps $STEPS --warmup 5 --cpu-seconds 0 --dist-config-steps 0 "$@" > gpurun_out/prof/${TAG}_bench.log 2>&1

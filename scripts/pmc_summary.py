@@ -1,5 +1,5 @@
 """Per-op and per-kernel-family HBM bytes from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of
-`bench.py --profile-passes 1 --profile-json P`.
+`bench.py --full --profile-passes 1 --profile-json P`.
 
     python scripts/pmc_summary.py <FETCH_SIZE dir> <WRITE_SIZE dir> <profile.json> > pmc_traffic.json
 

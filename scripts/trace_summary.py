@@ -4,7 +4,7 @@ set beside the `kernels` / `roofline` numbers bench.py printed for the same comm
 
     python scripts/trace_summary.py <rocprof output dir> <steps> [bench.log] > summary.json
 
-bench.py dispatches a torch spin kernel (`_trace_marker`) after warm-up, after the timed steps, and
+`bench.py --full` dispatches a torch spin kernel (`_trace_marker`) after warm-up, after the timed steps, and
 before the profile pass: segment 1 = the K timed steps, segment 3 = the profile passes.
 """
 import csv
