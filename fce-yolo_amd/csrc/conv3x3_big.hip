@@ -1,9 +1,9 @@
 // Big-tile 3x3 convolution fed by LDS-DMA (gfx950 global_load_lds_dwordx4); the m/l-scale 3x3 convs.
 // Replaces (reference, ultralytics/): nn/modules/conv.py:39-89 Conv.forward_fuse (3x3, BN folded by
-// utils/torch_utils.py:237-267) for cin % 32 == 0.  Variant code 0x800 | wm << 4 of fce_conv2d_variant.
+// utils/torch_utils.py:237-267) for cin % 32 == 0.  Variant kind 0x800 of fce_conv2d_variant (big3_encode at the end of the file).
 #include <vector>
 
-#include "conv_args.h"
+#include "conv_variant.h"
 
 namespace fce {
 
@@ -267,7 +267,13 @@ static int launch_big3_k(const ConvArgs& a, dim3 grid, hipStream_t s) {
   return FCE_OK;
 }
 
-int launch_big3(const ConvArgs& a, int wm, int ab, int nw, int stride, int n, hipStream_t s) {
+// Configurations: wm waves along the couts, ab weight-stage buffers, 4 waves per block (8-wave blocks were measured
+// and dropped); stride 2 needs wm 2 (LDS)
+static constexpr bool big3_ok(int s, int wm, int ab, int nw = 4) {
+  return nw == 4 && (ab == 2 || ab == 3) && (s == 1 ? (wm == 1 || wm == 2) : wm == 2);
+}
+
+static int launch_big3(const ConvArgs& a, int wm, int ab, int nw, int stride, int n, hipStream_t s) {
   FCE_CHECK(big3_ok(stride, wm, ab, nw) && a.cin % 32 == 0 && a.up == 0, "conv 3x3 big tile: bad configuration");
   const int th = (nw / wm) * 4;
   const int64_t tiles = int64_t((a.Wo + 15) / 16) * ((a.Ho + th - 1) / th) * n;
@@ -286,6 +292,31 @@ int launch_big3(const ConvArgs& a, int wm, int ab, int nw, int stride, int n, hi
   }
   if (rc != FCE_OK) return rc;
   return launch_status("conv3x3_big_kernel");
+}
+
+// ============================================================================ family: LDS-DMA big tile (kind 8)
+// coded 0x800 | wm << 4 | (ab - 2) << 12; the low nibble and the bits from 13 up stay 0
+struct Big3Cfg {
+  int wm, ab, rest;
+};
+static int big3_encode(int wm, int ab) { return 0x800 | (wm << 4) | ((ab - 2) << 12); }
+static Big3Cfg big3_decode(int code) { return {(code >> 4) & 15, ((code >> 12) & 1) + 2, (code & 0xF) | (code >> 13)}; }
+static bool big3_cfg_ok(const fce_conv_desc& d, int wm, int ab) {
+  return d.k == 3 && d.cin % 32 == 0 && d.up == 0 && big3_ok(d.stride, wm, ab);
+}
+
+// offered from 64 input and output channels; two waves along the couts from 128 output channels
+void big3_offer(const fce_conv_desc& d, int det_box, CodeList& out) {
+  if (det_box || d.cin < 64 || d.cout < 64) return;
+  for (int ab : {2, 3})
+    for (int wm : {1, 2})
+      if (big3_cfg_ok(d, wm, ab) && (wm == 1 || d.cout >= 128)) out.add(big3_encode(wm, ab));
+}
+
+int big3_launch(const ConvCall& c, int code) {
+  const Big3Cfg t = big3_decode(code);
+  FCE_CHECK(big3_cfg_ok(c.d, t.wm, t.ab) && c.out_kind == OUT_F16 && t.rest == 0, "conv: bad big-tile 3x3 hint");
+  return launch_big3(c.a, t.wm, t.ab, 4, c.d.stride, c.n, c.s);
 }
 
 }  // namespace fce

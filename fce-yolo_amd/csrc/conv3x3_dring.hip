@@ -1,17 +1,18 @@
-// Persistent 3x3 convolution ring fed by LDS-DMA (variant code 0xD00 | rp << 4 | (cpw - 1) << 3 | (sub - 1) << 2 |
-// (nbuf - 2) of fce_conv2d_variant).
+// Persistent 3x3 convolution ring fed by LDS-DMA (variant kind 0xD00 of fce_conv2d_variant: dring_encode at the end
+// of the file).
 // Replaces (reference, ultralytics/): nn/modules/conv.py:39-89 Conv.forward_fuse (3x3, BN folded by
-// utils/torch_utils.py:237-267) for cin 32 / 64, like conv3x3_ring_kernel (csrc/conv.hip), bitwise identical to it.
+// utils/torch_utils.py:237-267) for cin 32 / 64, like conv3x3_ring_kernel (csrc/conv3x3_ring.hip), bitwise identical
+// to it.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "conv_args.h"
+#include "conv_variant.h"
 
 namespace fce {
 
-// slot swizzle of the tile kernels (conv.hip tile_slot): an involution of the 4 * KP pieces of position u
+// slot swizzle of the tile kernels (conv_args.h tile_slot): an involution of the 4 * KP pieces of position u
 template <int KP>
 __device__ __forceinline__ int dr_slot(int u, int q) {
   // KP 4 (16 pieces, 256 bytes per position: every position starts on bank 0): q ^ 2 (u & 7).  The lanes of a
@@ -37,7 +38,8 @@ static int dr_blocks_per_cu(const void* kernel, size_t lds) {
   return std::max(1, n);
 }
 
-// persistent slots per XCD (conv.hip ring_slots: tiles / 8 at most, the resident blocks of one XCD's CUs)
+// persistent slots per XCD (conv_variant.h ring_slots, without its FCE_PERSIST_OCC cap: tiles / 8 at most, the
+// resident blocks of one XCD's CUs)
 static int dr_slots(int units, int gy, int occ) {
   static const int cus = [] {
     int d = 0, n = 0;
@@ -50,8 +52,41 @@ static int dr_slots(int units, int gy, int occ) {
   return std::max(1, std::min((units + 7) / 8, cus * occ / std::max(1, gy)));
 }
 
+template <int S, int RP, int NCH, int WRW = 1>
+struct Dring3Geom {
+  static constexpr int TW = 16, TH = WRW * RP;  // WRW waves along the rows (2 when each wave owns 2 cout tiles)
+  static constexpr int RI = (TH - 1) * S + 3, CI = (TW - 1) * S + 3;
+  static constexpr int NQ = 4 * NCH, NE = RI * CI * NQ;
+  static constexpr int NINS = (NE + 63) / 64;  // 1 KiB copy instructions per tile
+  static constexpr int DPW = (NINS + 3) / 4;   // per wave (4 waves), padded
+  static constexpr int BUF = DPW * 4 * 64;     // pieces per tile buffer
+};
+
+static constexpr bool dring3_fits(int s, int rp, int nch, int nbuf, int cpw = 1, int sub = 1) {
+  return size_t(nbuf) * ((((((cpw * rp * sub - 1) * s + 3) * (15 * s + 3) * 4 * nch + 63) / 64 + 3) / 4) * 4 * 64) * 16 <=
+             80 * 1024 &&       // two blocks per CU
+         // two cout tiles of 64-channel A fragments: 1- and 2-row tiles with three buffers only (253 VGPRs at 2 rows;
+         // more rows or buffers spill at two waves per SIMD)
+         (cpw == 1 || nch == 1 || (nch == 2 && rp <= 2 && nbuf == 3 && sub == 1)) &&
+         (rp < 8 || (nch == 1 && nbuf == 3)) &&  // 8-row tiles of 64-channel fragments spill too (or with four buffers)
+         // 128 channels (36 A fragments in registers): stride-2 one-row tiles only; the two-row stride-1 ones spilled
+         // (31.2 against 24.3 us, r06al)
+         (nch < 4 || (s == 2 && rp == 1)) &&
+         (sub == 1 || (sub == 2 && rp * sub <= 8));  // sub-tiles: 8 rows of held residuals at most
+}
+// the candidates offered: two buffers or one-row tiles only for the 128-channel tiles, which need them to fit (at 32 /
+// 64 channels the two-buffer ones are the big stride-2 tiles, which spill), and for the 64-channel two-cout-tile ones
+// (0xd19: 2 x 1 rows per block; 0xd29 25.6 against 25.9-26.3 us for 0xd41 at 64 -> 64 80 x 80, its MFMA phase 1.97k
+// against 2.16k clocks per tile at half the LDS reads, r06av); two sub-tiles only for the 32-channel
+// stride-1 convs, the one place they measured ahead (48.4 against 49.9 us at 160 x 160; 64 -> 64 at 80 x 80 and the
+// stride-2 ones slower, the 64-channel 8-row tiles spilling: profiles/r06_dring_probe.txt)
+static constexpr bool dring3_offer(int s, int rp, int nch, int nbuf, int cpw = 1, int sub = 1) {
+  return dring3_fits(s, rp, nch, nbuf, cpw, sub) && (nch == 4 || (nbuf > 2 && (rp > 1 || (cpw == 2 && nch == 2)))) &&
+         (nbuf > 2 || !dring3_fits(s, rp, nch, 3, cpw, sub)) && (sub == 1 || (nbuf > 2 && rp >= 2 && nch == 1 && s == 1));
+}
+
 // ============================================================================ 3x3, persistent, LDS-DMA ring
-// conv3x3_ring_kernel (conv.hip: one cout tile per wave, its 9 * NCH A fragments in registers, TH = RP row x 16
+// conv3x3_ring_kernel (conv3x3_ring.hip: one cout tile per wave, its 9 * NCH A fragments in registers, TH = RP row x 16
 // column tiles, the same K order, so bitwise identical) with the staged input copied global -> LDS by LDS-DMA
 // (buffer_load_dwordx4 ... lds) into a ring of NBUF tile buffers, NBUF - 1 tiles ahead of the MFMAs, instead of one
 // tile ahead through registers.  The register ring keeps ~16-21 KiB per block in flight for ~0.5 us of MFMAs; against
@@ -344,7 +379,7 @@ static int launch_dring3_c(const ConvArgs& a, int rp, int nbuf, int cpw, int sub
 }
 
 // nbuf: tile buffers of the LDS-DMA ring (nbuf - 1 tiles of input in flight ahead of the MFMAs); cpw: cout tiles per wave
-int launch_dring3(const ConvArgs& a0, int rp, int nbuf, int cpw, int sub, int stride, hipStream_t s) {
+static int launch_dring3(const ConvArgs& a0, int rp, int nbuf, int cpw, int sub, int stride, hipStream_t s) {
   FCE_CHECK((a0.cin == 32 || a0.cin == 64 || a0.cin == 128) && a0.cout % (16 * cpw) == 0 &&
                 (rp == 1 || rp == 2 || rp == 4 || (rp == 8 && cpw == 1)) && nbuf >= 2 && nbuf <= 4 &&
                 (cpw == 1 || cpw == 2) && (sub == 1 || sub == 2) && (stride == 1 || stride == 2) &&
@@ -366,6 +401,51 @@ int launch_dring3(const ConvArgs& a0, int rp, int nbuf, int cpw, int sub, int st
   return nch == 1 ? launch_dring3_c<2, 1>(a, rp, nbuf, cpw, sub, int(ntiles), s)
                   : nch == 2 ? launch_dring3_c<2, 2>(a, rp, nbuf, cpw, sub, int(ntiles), s)
                              : launch_dring3_c<2, 4>(a, rp, nbuf, cpw, sub, int(ntiles), s);
+}
+
+// ============================================================================ family: LDS-DMA ring (kind 13)
+// coded 0xD00 | rp << 4 | (cpw - 1) << 3 | (sub - 1) << 2 | (nbuf - 2): cin 32 / 64 / 128, cpw cout tiles per wave
+// (1: 4 waves along the couts; 2: 2 x 2 waves), sub x rp rows x 16 columns per wave and tile (sub sub-tiles of rp rows,
+// one after the other, per barrier), nbuf LDS tile buffers (nbuf - 1 tiles of input in flight)
+struct DringCfg {
+  int rp, nbuf, cpw, sub;
+};
+static int dring_encode(const DringCfg& t) {
+  return 0xD00 | (t.rp << 4) | ((t.cpw - 1) << 3) | ((t.sub - 1) << 2) | (t.nbuf - 2);
+}
+static DringCfg dring_decode(int code) {
+  return {(code >> 4) & 15, (code & 3) + 2, ((code >> 3) & 1) + 1, ((code >> 2) & 1) + 1};
+}
+static bool dring_cfg_ok(const fce_conv_desc& d, const DringCfg& t) {
+  return d.k == 3 && (d.cin == 32 || d.cin == 64 || d.cin == 128) && d.cout % (16 * t.cpw) == 0 && d.up == 0 &&
+         (t.rp == 1 || t.rp == 2 || t.rp == 4 || (t.rp == 8 && t.cpw == 1)) && t.nbuf >= 2 && t.nbuf <= 4 &&
+         dring3_offer(d.stride, t.rp, d.cin / 32, t.nbuf, t.cpw, t.sub);
+}
+
+// FCE_NO_DRING=1 (A/B runs, read per call) drops them, as FCE_NO_RING=1 drops every persistent variant
+void dring_offer(const fce_conv_desc& d, int det_box, CodeList& out) {
+  if (det_box || no_ring() || env_on("FCE_NO_DRING")) return;
+  for (int cpw : {1, 2})
+    for (int rp : {1, 2, 4, 8})
+      for (int sub : {1, 2})
+        for (int nbuf : {2, 3, 4}) {
+          const DringCfg t{rp, nbuf, cpw, sub};
+          if (dring_cfg_ok(d, t)) out.add(dring_encode(t));
+        }
+}
+
+int dring_launch(const ConvCall& c, int code) {
+  const DringCfg t = dring_decode(code);
+  const fce_conv_desc& d = c.d;
+  const ConvArgs& a = c.a;
+  FCE_CHECK(dring_cfg_ok(d, t) && c.out_kind == OUT_F16, "conv: bad 3x3 LDS-DMA ring hint");
+  // the copies and the unconditional stores address input and output through buffer resources (byte offsets < 2^31),
+  // the output as 8-byte pieces: other views take the register ring, which gives the same bits
+  if (!a.vec_ok || int64_t(a.P) * a.ycs * 2 >= (int64_t(1) << 31) ||
+      int64_t(a.N) * a.Hs * a.Ws * a.xcs * 2 >= (int64_t(1) << 31))  // cin 128: the implicit-GEMM kernel (same bits)
+    return d.cin == 128 ? conv2d_impl(d, c.x, c.w, c.bias, c.res, c.y, c.det, c.s, -1, c.dup, c.duplo)
+                        : launch_ring3(a, std::max(t.rp, 2) > 4 ? 4 : std::max(t.rp, 2), 1, d.stride, c.s);
+  return launch_dring3(a, t.rp, t.nbuf, t.cpw, t.sub, d.stride, c.s);
 }
 
 }  // namespace fce

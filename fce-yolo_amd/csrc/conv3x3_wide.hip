@@ -1,6 +1,6 @@
 // Wide-tile 3x3 convolution with per-K-step weight staging; the m/l-scale dense 3x3 convs.
 // Replaces (reference, ultralytics/): nn/modules/conv.py:39-89 Conv.forward_fuse (3x3, BN folded by
-// utils/torch_utils.py:237-267) for cin % 32 == 0.  Variant code 0xA00 | log2(cw) << 4 of fce_conv2d_variant.
+// utils/torch_utils.py:237-267) for cin % 32 == 0.  Variant kind 0xA00 of fce_conv2d_variant (wide3_encode at the end of the file).
 //
 // Every wave owns 64 couts x 64 output pixels (4 cout tiles x 4 output rows of 16 columns: 16 MFMAs per 4 A +
 // 4 B fragment reads from LDS); the block is CW x (4 / CW) such waves, i.e. 64 CW couts x 16 (4 / CW) rows of
@@ -16,7 +16,7 @@
 // Plain global loads + ds_write instead of LDS-DMA: the DMA copies' issue cost (60-185 clocks each, stage
 // clocks of conv3x3_big.hip) is what held that kernel's matrix core idle.  Same K order and fragments as
 // every other variant: bitwise identical.
-#include "conv_args.h"
+#include "conv_variant.h"
 
 namespace fce {
 
@@ -176,9 +176,9 @@ static int launch_wide_k(const ConvArgs& a, dim3 grid, hipStream_t s) {
   return FCE_OK;
 }
 
-bool wide3_ok(int stride, int cw) { return stride == 1 ? (cw == 1 || cw == 2 || cw == 4) : stride == 2 && cw == 2; }
+static bool wide3_ok(int stride, int cw) { return stride == 1 ? (cw == 1 || cw == 2 || cw == 4) : stride == 2 && cw == 2; }
 
-int launch_wide3(const ConvArgs& a, int cw, int stride, int n, hipStream_t s) {
+static int launch_wide3(const ConvArgs& a, int cw, int stride, int n, hipStream_t s) {
   FCE_CHECK(wide3_ok(stride, cw) && a.cin % 32 == 0 && a.up == 0, "conv 3x3 wide tile: bad configuration");
   const int th = (4 / cw) * 4;
   const int64_t tiles = int64_t((a.Wo + 15) / 16) * ((a.Ho + th - 1) / th) * n;
@@ -194,6 +194,32 @@ int launch_wide3(const ConvArgs& a, int cw, int stride, int n, hipStream_t s) {
     rc = launch_wide_k<2, 2>(b, grid, s);
   if (rc != FCE_OK) return rc;
   return launch_status("conv3x3_wide_kernel");
+}
+
+// ============================================================================ family: wide tile (kind 10)
+// coded 0xA00 | log2(cw) << 4: 64 cw couts x 16 (4 / cw) rows per block; every other bit stays 0
+struct Wide3Cfg {
+  int cw, rest;
+};
+static int wide3_encode(int cw) { return 0xA00 | (ilog2(cw) << 4); }
+static Wide3Cfg wide3_decode(int code) { return {1 << ((code >> 4) & 3), (code & 0xF) | ((code >> 6) ^ (0xA00 >> 6))}; }
+static bool wide3_cfg_ok(const fce_conv_desc& d, int cw) {
+  return d.k == 3 && d.cin % 32 == 0 && d.up == 0 && wide3_ok(d.stride, cw);
+}
+
+// opt-in, FCE_WIDE3=1 (read per call: the variant tests switch it on mid-process): measured at parity or slower on
+// every m/l shape; from 64 input and output channels
+void wide3_offer(const fce_conv_desc& d, int det_box, CodeList& out) {
+  if (det_box || d.cin < 64 || d.cout < 64 || !env_on("FCE_WIDE3")) return;
+  const int cotiles = (d.cout + 15) / 16;
+  for (int cw : {1, 2, 4})
+    if (wide3_cfg_ok(d, cw) && cotiles_want(4 * cw, cotiles)) out.add(wide3_encode(cw));
+}
+
+int wide3_launch(const ConvCall& c, int code) {
+  const Wide3Cfg t = wide3_decode(code);
+  FCE_CHECK(wide3_cfg_ok(c.d, t.cw) && c.out_kind == OUT_F16 && t.rest == 0, "conv: bad wide-tile 3x3 hint");
+  return launch_wide3(c.a, t.cw, c.d.stride, c.n, c.s);
 }
 
 }  // namespace fce

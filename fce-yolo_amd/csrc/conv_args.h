@@ -1,5 +1,6 @@
-// Shared by the dense conv translation units (conv.hip, conv3x3_big.hip): the kernel argument block,
-// the output kinds, the zero line, and the 3x3 halo-tile helpers (image layout, block order, epilogue).
+// Shared by the dense conv translation units (conv.hip and the family files, through conv_variant.h): the kernel
+// argument block, the output kinds, the zero line, and the device-side helpers (the dense epilogue; the 3x3
+// halo-tile image layout, block order and epilogue).
 #pragma once
 #include "common.h"
 
@@ -54,6 +55,14 @@ template <int S, int CI>
 __device__ __forceinline__ int tile_col(int c) {
   if (S == 1) return c;
   return (c & 1) ? (CI + 1) / 2 + (c >> 1) : (c >> 1);
+}
+
+// Slot swizzle of the 4*KP 16-byte pieces of position u in the staged tile of the 3x3 tile and ring kernels:
+// q ^ ((u >> 1) & 3) for KP = 1, q ^ (u & 6) for KP = 2 (both conflict-free for the B-fragment reads at any
+// alignment; checked exhaustively over the ds_read_b128 lane groups).
+template <int KP>
+__device__ __forceinline__ int tile_slot(int u, int q) {
+  return KP == 1 ? (q ^ ((u >> 1) & 3)) : (q ^ (u & 6));
 }
 
 // XCD-aware block order of the 3x3 tile kernels: the grid is 1-D (tiles x cout groups); block b runs on
@@ -424,60 +433,5 @@ __device__ __forceinline__ int64_t conv1x1_src(const ConvArgs& a, int pix) {
   const int oy = r / a.Wo, ox = r - oy * a.Wo;
   return nhwc_off(n, oy >> a.up, ox >> a.up, a.Hs, a.Ws, a.xcs);
 }
-
-// Big-tile LDS-DMA 3x3 configurations (conv3x3_big.hip), coded 0x800 | wm << 4 | (ab - 2) << 12: wm waves along
-// the couts, ab weight-stage buffers, 4 waves per block (8-wave blocks were measured and dropped);
-// stride 2 needs wm 2 (LDS)
-static constexpr bool big3_ok(int s, int wm, int ab, int nw = 4) {
-  return nw == 4 && (ab == 2 || ab == 3) && (s == 1 ? (wm == 1 || wm == 2) : wm == 2);
-}
-int launch_big3(const ConvArgs& a, int wm, int ab, int nw, int stride, int n, hipStream_t s);
-// Persistent 3x3 ring fed by LDS-DMA (conv3x3_dring.hip), coded 0xD00 | rp << 4 | (cpw - 1) << 3 | (sub - 1) << 2 |
-// (nbuf - 2): cin 32 / 64 / 128, cpw cout tiles per wave (1: 4 waves along the couts; 2: 2 x 2 waves), sub x rp rows x
-// 16 columns per wave and tile (sub sub-tiles of rp rows, one after the other, per barrier), nbuf LDS tile buffers
-// (nbuf - 1 tiles of input in flight)
-template <int S, int RP, int NCH, int WRW = 1>
-struct Dring3Geom {
-  static constexpr int TW = 16, TH = WRW * RP;  // WRW waves along the rows (2 when each wave owns 2 cout tiles)
-  static constexpr int RI = (TH - 1) * S + 3, CI = (TW - 1) * S + 3;
-  static constexpr int NQ = 4 * NCH, NE = RI * CI * NQ;
-  static constexpr int NINS = (NE + 63) / 64;  // 1 KiB copy instructions per tile
-  static constexpr int DPW = (NINS + 3) / 4;   // per wave (4 waves), padded
-  static constexpr int BUF = DPW * 4 * 64;     // pieces per tile buffer
-};
-
-static constexpr bool dring3_fits(int s, int rp, int nch, int nbuf, int cpw = 1, int sub = 1) {
-  return size_t(nbuf) * ((((((cpw * rp * sub - 1) * s + 3) * (15 * s + 3) * 4 * nch + 63) / 64 + 3) / 4) * 4 * 64) * 16 <=
-             80 * 1024 &&       // two blocks per CU
-         // two cout tiles of 64-channel A fragments: 1- and 2-row tiles with three buffers only (253 VGPRs at 2 rows;
-         // more rows or buffers spill at two waves per SIMD)
-         (cpw == 1 || nch == 1 || (nch == 2 && rp <= 2 && nbuf == 3 && sub == 1)) &&
-         (rp < 8 || (nch == 1 && nbuf == 3)) &&  // 8-row tiles of 64-channel fragments spill too (or with four buffers)
-         // 128 channels (36 A fragments in registers): stride-2 one-row tiles only; the two-row stride-1 ones spilled
-         // (31.2 against 24.3 us, r06al)
-         (nch < 4 || (s == 2 && rp == 1)) &&
-         (sub == 1 || (sub == 2 && rp * sub <= 8));  // sub-tiles: 8 rows of held residuals at most
-}
-// the candidates offered: two buffers or one-row tiles only for the 128-channel tiles, which need them to fit (at 32 /
-// 64 channels the two-buffer ones are the big stride-2 tiles, which spill), and for the 64-channel two-cout-tile ones
-// (0xd19: 2 x 1 rows per block; 0xd29 25.6 against 25.9-26.3 us for 0xd41 at 64 -> 64 80 x 80, its MFMA phase 1.97k
-// against 2.16k clocks per tile at half the LDS reads, r06av); two sub-tiles only for the 32-channel
-// stride-1 convs, the one place they measured ahead (48.4 against 49.9 us at 160 x 160; 64 -> 64 at 80 x 80 and the
-// stride-2 ones slower, the 64-channel 8-row tiles spilling: profiles/r06_dring_probe.txt)
-static constexpr bool dring3_offer(int s, int rp, int nch, int nbuf, int cpw = 1, int sub = 1) {
-  return dring3_fits(s, rp, nch, nbuf, cpw, sub) && (nch == 4 || (nbuf > 2 && (rp > 1 || (cpw == 2 && nch == 2)))) &&
-         (nbuf > 2 || !dring3_fits(s, rp, nch, 3, cpw, sub)) && (sub == 1 || (nbuf > 2 && rp >= 2 && nch == 1 && s == 1));
-}
-int launch_dring3(const ConvArgs& a, int rp, int nbuf, int cpw, int sub, int stride, hipStream_t s);
-// Wide-tile 3x3 (conv3x3_wide.hip), coded 0xA00 | log2(cw) << 4: 64 cw couts x 16 (4 / cw) rows per block
-bool wide3_ok(int stride, int cw);
-int launch_wide3(const ConvArgs& a, int cw, int stride, int n, hipStream_t s);
-// Big-tile implicit GEMM (conv_big.hip): 16 wr wc couts x 64 (nw / wc) pixels per nw-wave block (nw 8: one block per
-// CU; nw 4: two; wr = cout tiles per wave, 8, or 4 with nw 4); 1x1 coded 0xB00 | log2(wc) << 4 | (nw == 4) << 6 |
-// (wr == 4) << 7, 3x3 (cin % 32 == 0, stride 1 / 2, plain fp16 output) 0xC00 | the same bits
-bool big1_ok(int wc);
-bool big1_split_ok(int wc, int nw, int wr);
-int launch_big1(const ConvArgs& a, int out_kind, int wc, int nw, int wr, bool split, hipStream_t s);  // split: | 0x20
-int launch_big3g(const ConvArgs& a, int wc, int nw, int wr, int stride, bool split, hipStream_t s);
 
 }  // namespace fce

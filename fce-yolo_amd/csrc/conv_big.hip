@@ -2,8 +2,8 @@
 // Replaces (reference, ultralytics/): nn/modules/conv.py:39-89 Conv.forward_fuse (BN folded by
 // utils/torch_utils.py:237-267) for 1x1 kernels -- the C2f / C3k / SPPF / C2PSA cv1 / cv2 / FFN pointwise convs, the
 // BiFPN realign convs (fce_block.py:24-38), nn.Upsample feeding a 1x1 conv -- and for 3x3 kernels with cin % 32 == 0
-// (the stride-2 downsampling convs and the wide bottleneck convs).  Variant codes 0xB00 (1x1) / 0xC00 (3x3) |
-// log2(wc) << 4 | split << 5 | (nw == 4) << 6 | (wr == 4) << 7.
+// (the stride-2 downsampling convs and the wide bottleneck convs).  Variant kinds 0xB00 (1x1) / 0xC00 (3x3):
+// big1_encode / big3g_encode / big_decode at the end of the file.
 //
 // Geometry: NW waves per block (8: one block per CU; 4: two per CU, so one block's prologue and staged epilogue run
 // under the other's K loop), WC waves along the couts, each owning WR cout tiles (8: 128 couts; 4: 64, 4-wave blocks
@@ -23,7 +23,7 @@
 // BiFPN weighted store / accumulate, Detect cls): bitwise identical to every other variant of the same conv.
 #include <algorithm>
 
-#include "conv_args.h"
+#include "conv_variant.h"
 
 namespace fce {
 
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_big_kernel(Conv
   conv_epilogue<WR, 4, OUT>(a, acc, p0 + wp * 64, ct_blk + wc * WR, col, grp);
 }
 
-bool big1_ok(int wc) { return wc == 1 || wc == 2; }
+static bool big1_ok(int wc) { return wc == 1 || wc == 2; }
 
 template <int KS, int S, int WC, int NW, int OUT, int DIAG, int WR = 8, int RBD = 0>
 static int launch_big_d(const ConvArgs& a, dim3 grid, hipStream_t s) {
@@ -381,7 +381,7 @@ static ConvArgs big_grid(const ConvArgs& a0, int wc, int nw, int wr, dim3& grid)
 static constexpr int big1_rbd(int wc, int nw, int wr) {
   return nw == 8 ? (wc == 2 ? 6 : 4) : wr == 4 ? (wc == 2 ? 6 : 4) : (wc == 2 ? 4 : 0);
 }
-bool big1_split_ok(int wc, int nw, int wr) { return big1_rbd(wc, nw, wr) > 0; }
+static bool big1_split_ok(int wc, int nw, int wr) { return big1_rbd(wc, nw, wr) > 0; }
 
 int launch_big1(const ConvArgs& a0, int out_kind, int wc, int nw, int wr, bool split, hipStream_t s) {
   FCE_CHECK(big1_ok(wc) && (nw == 8 || nw == 4) && (wr == 8 || (wr == 4 && nw == 4)) && a0.cin % 8 == 0 &&
@@ -438,6 +438,62 @@ int launch_big3g(const ConvArgs& a0, int wc, int nw, int wr, int stride, bool sp
                    : launch_big3g_s<2, 4, 4>(a, wc, split, grid, s);
   if (rc != FCE_OK) return rc;
   return launch_status("conv_big_kernel");
+}
+
+// ============================================================================ families: 1x1 (kind 11), 3x3 (kind 12)
+// coded 0xB00 (1x1) / 0xC00 (3x3) | log2(wc) << 4 | split << 5 | (nw == 4) << 6 | (wr == 4) << 7; the low nibble
+// stays 0.  16 wr wc couts x 64 (nw / wc) pixels per nw-wave block: nw 8 one block per CU, nw 4 two; wr = cout
+// tiles per wave, 8, or 4 with nw 4; split: two rings, the pixels in the deep one
+struct BigCfg {
+  int wc, nw, wr;
+  bool split;
+  int low;
+};
+static int big_bits(int wc, int nw, int wr, bool split) {
+  return (ilog2(wc) << 4) | (int(split) << 5) | (int(nw == 4) << 6) | (int(wr == 4) << 7);
+}
+static int big1_encode(int wc, int nw, int wr, bool split) { return 0xB00 | big_bits(wc, nw, wr, split); }
+static int big3g_encode(int wc, int nw, int wr, bool split) { return 0xC00 | big_bits(wc, nw, wr, split); }
+static BigCfg big_decode(int code) {
+  return {1 << ((code >> 4) & 1), (code >> 6) & 1 ? 4 : 8, (code >> 7) & 1 ? 4 : 8, bool((code >> 5) & 1), code & 0x0F};
+}
+static bool big_cfg_ok(const BigCfg& t) { return t.low == 0 && big1_ok(t.wc) && (t.wr == 8 || t.nw == 4); }
+static bool big1_shape_ok(const fce_conv_desc& d) { return d.k == 1 && d.stride == 1; }
+static bool big3g_shape_ok(const fce_conv_desc& d) { return d.k == 3 && d.cin % 32 == 0 && d.up == 0; }
+
+// split-major (one ring first), then 8 waves x 8 cout tiles, 4 x 8, 4 x 4, then wc from wc_min; offered from 64
+// input and output channels, never for the Detect box conv
+static void big_offer(int (*encode)(int, int, int, bool), int wc_min_split, const fce_conv_desc& d, int det_box, CodeList& out) {
+  if (det_box || d.cin < 64 || d.cout < 64) return;
+  const int cotiles = (d.cout + 15) / 16;
+  struct {
+    int nw, wr;
+  } const shapes[] = {{8, 8}, {4, 8}, {4, 4}};
+  for (bool split : {false, true})
+    for (const auto& sh : shapes)
+      for (int wc : {1, 2}) {
+        if (split && (wc < wc_min_split || !big1_split_ok(wc, sh.nw, sh.wr))) continue;
+        if (cotiles_want(sh.wr * wc, cotiles)) out.add(encode(wc, sh.nw, sh.wr, split));
+      }
+}
+void big1_offer(const fce_conv_desc& d, int det_box, CodeList& out) {
+  if (big1_shape_ok(d)) big_offer(big1_encode, 1, d, det_box, out);
+}
+// FCE_NO_GEMM3=1 (diagnostics / A-B runs, read per call) drops the 3x3 candidates; their split rings: wc 2 only
+void big3g_offer(const fce_conv_desc& d, int det_box, CodeList& out) {
+  if (big3g_shape_ok(d) && !env_on("FCE_NO_GEMM3")) big_offer(big3g_encode, 2, d, det_box, out);
+}
+
+int big1_launch(const ConvCall& c, int code) {
+  const BigCfg t = big_decode(code);
+  FCE_CHECK(big1_shape_ok(c.d) && c.out_kind != OUT_DFL && big_cfg_ok(t), "conv: bad big-tile 1x1 hint");
+  return launch_big1(c.a, c.out_kind, t.wc, t.nw, t.wr, t.split, c.s);
+}
+
+int big3g_launch(const ConvCall& c, int code) {
+  const BigCfg t = big_decode(code);
+  FCE_CHECK(big3g_shape_ok(c.d) && c.out_kind == OUT_F16 && big_cfg_ok(t), "conv: bad big-tile 3x3 (implicit GEMM) hint");
+  return launch_big3g(c.a, t.wc, t.nw, t.wr, c.d.stride, t.split, c.s);
 }
 
 }  // namespace fce

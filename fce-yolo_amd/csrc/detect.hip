@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(DecodeArgs a) {
     const float* bx = L.box + (int64_t(n) * L.h * L.w + p) * L.bcs;
     float dist[4];
     for (int s = 0; s < 4; ++s) {
-      // same reduction tree as the fused conv epilogue (conv.hip OUT_DFL): four partial sums of
+      // same reduction tree as the fused conv epilogue (conv_args.h conv_epilogue, OUT_DFL): four partial sums of
       // 4 consecutive bins, combined as (g0 + g1) + (g2 + g3), so both paths agree bit for bit
       const float* b = bx + s * a.reg_max;
       float mx = -INFINITY;

@@ -1,9 +1,13 @@
 """Per-op autotune report of the bench workload: chosen kernel variant, and every candidate's time.
 
     python scripts/tune_report.py [--model yolo11n-fce.yaml] [--batch 32] [--imgsz 640] > report.txt
-Variant codes: rc | rp << 4 (implicit GEMM), 0x100 | .. (3x3 LDS tile, cin % 32 == 0), 0x200 | ..
-(3x3 LDS tile, small cin), 0x300 | .. (1x1 streaming), 0x400 | .. | log2(wp) << 12 (1x1 LDS tile), 0x500 (1x1 ring), 0x700 | log2(wp) << 12 (1x1 big tile, K-pipelined),
-100 + v (depthwise variant v).
+Variant codes: kind = (code >> 8) & 15 names the kernel family, in the order of the kFamilies table of
+csrc/conv.hip (which is also the order of the candidates below): 0 implicit GEMM, 3 1x1 streaming, 4 1x1 LDS tile,
+5 1x1 ring, 0xB 1x1 256-wide tile, 7 1x1 big tile (K-pipelined), 2 3x3 LDS tile (small cin), 6 3x3 ring,
+0xD 3x3 LDS-DMA ring, 9 3x3 32x32x16 ring, 1 3x3 LDS tile (cin % 32 == 0), 8 3x3 LDS-DMA big tile,
+0xC 3x3 256-wide implicit GEMM, 0xA 3x3 wide tile; 100 + v is depthwise variant v.  The other bits are the
+family's own: the encode / decode pair in the family's file under csrc/ (csrc/conv_variant.h lists them) is the
+authority.
 """
 import argparse
 import ctypes as C

@@ -1599,6 +1599,27 @@ def test_every_op_variant_bitwise_in_model(cfg, batch, imgsz, device, monkeypatc
     assert tried > 100 and not bad, bad
 
 
+def test_net_op_variant_lists_match_golden(device, monkeypatch):
+    """fce_net_op_variants of every conv / conv-detect op of the smoke() model (yolo11n-fce, 160x160, batch 2,
+    planned without autotuning) returns exactly the recorded list, element for element: the only way to the
+    Detect box (det_box) candidate lists (tests/golden/make_golden_conv_variants.py)."""
+    import json
+
+    from conftest import GOLDEN
+
+    for knob in ("FCE_TILE3AL", "FCE_WIDE3", "FCE_RING32", "FCE_NO_GEMM3", "FCE_NO_DRING"):
+        monkeypatch.delenv(knob, raising=False)
+    rec = json.loads((GOLDEN / "conv_variants.json").read_text())
+    want = {i: rec["net_lists"][j] for i, j in rec["net_ops"].items()}
+    model = cases.seeded_model("yolo11n-fce.yaml", 0).to(device)
+    eng = Engine(model, 2, 160, device, autotune=False)
+    got = {str(i): eng.variants(i) for i in range(eng.num_ops())}
+    got = {i: codes for i, codes in got.items() if codes}
+    assert len(want) > 50 and set(got) == set(want)
+    bad = [(i, [hex(c) for c in got[i]], [hex(c) for c in want[i]]) for i in want if got[i] != want[i]]
+    assert not bad, bad[:3]
+
+
 @pytest.mark.parametrize("hw", [(20, 23), (9, 7), (16, 16), (33, 20)])
 def test_c2psa_multi_chunk_vs_oracle(hw, device):
     """C2PSA attention over more keys than one 256-key LDS chunk (and ragged 64-key tiles) vs the fp64

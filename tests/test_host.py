@@ -3,6 +3,7 @@ layout of the drop-in modules, and the C-ABI library (loads, exports every decla
 host-only packing).  No GPU compute here."""
 
 import ctypes as C
+import json
 import re
 from pathlib import Path
 
@@ -174,6 +175,38 @@ def test_conv_variant_enumeration(cin, cout, k, stride, kinds_in, kinds_out):
     assert nv >= 2 and len(set(codes[:nv])) == nv
     assert kinds <= {0x000, 0x100, 0x200, 0x300, 0x400, 0x500, 0x600, 0x700, 0x800, 0xA00, 0xB00, 0xC00, 0xD00}
     assert kinds_in <= kinds and not (kinds_out & kinds)
+
+
+def _golden_conv_variants():
+    """tests/golden/make_golden_conv_variants.py as a module: the grids, the env sets and the child-process runner."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("make_golden_conv_variants",
+                                                  ROOT / "tests" / "golden" / "make_golden_conv_variants.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_conv_variant_lists_match_golden():
+    """fce_conv_variants returns exactly the recorded candidate list (same codes, same order, same length) for
+    every shape of the dense and depthwise grids under every env set, each env set in a fresh child process
+    (FCE_NO_RING is read once per process); and a cap-16 call returns the first 16 codes of the full list."""
+    G = _golden_conv_variants()
+    rec = json.loads(G.FIXTURE.read_text())
+    assert rec["cap"] == G.CAP and tuple(rec["truncated_call"]) == G.TRUNCATED
+    assert set(rec["host"]) == set(G.ENV_SETS)
+    cin, cout, k, stride, up, in_w, cap = G.TRUNCATED
+    for name in G.ENV_SETS:
+        lists = G.child_lists(name)
+        trunc = lists.pop("truncated")
+        want = [rec["lists"][i] for i in rec["host"][name]["entries"]]  # in grid order, as `lists`
+        assert len(lists) == len(want) == 780, name
+        bad = [(key, [hex(c) for c in codes], [hex(c) for c in w]) for (key, codes), w in zip(lists.items(), want)
+               if codes != w]
+        assert not bad, (name, len(bad), bad[:2])
+        full = lists[f"{cin},{cout},{k},{stride},{up},{in_w}"]
+        assert len(full) > cap and trunc == full[:cap] == rec["host"][name]["truncated"], name
 
 
 def test_error_path_reports_message():
