@@ -293,3 +293,85 @@ def designed_model(key, fx):
     model.load_state_dict(sd)
     x = torch.rand(b, 3, s, s, generator=torch.Generator().manual_seed(int(fx["x_seed"])))
     return model.eval(), x
+
+
+# ---------------------------------------------------------------- coordinate-attention path cases (test_gpu_paths.py)
+COORD_CLS = {"Bi": M.BiCoordCrossAtt, "Att": M.CoordAtt, "Cross": M.CoordCrossAtt}
+
+
+def build_coord(kind, args, seed):
+    """One of the three coordinate-attention drop-ins with seeded weights, as build_op makes them (BN eps 1e-3)."""
+    mod = COORD_CLS[kind](*args)
+    mod.load_state_dict(seeded_state_dict([(k, v.shape) for k, v in mod.state_dict().items()], seed))
+    for m in mod.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            m.eps = 1e-3
+    return mod.eval()
+
+
+def sharpened_input(shape, seed):
+    """randn fp16 input whose last row, last column and rows 15 / 16 (where they exist) are 4 x larger: a pooled
+    mean that drops or double-counts one of them moves by far more than its rounding."""
+    x = torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+    h, w = shape[2:]
+    for r in sorted({h - 1, 15, 16}):
+        if 0 <= r < h:
+            x[:, :, r] *= 4
+    x[:, :, :, w - 1] *= 4
+    return x.half()
+
+
+def _axial(q, k, v, scale):
+    return ((q @ k) * scale).softmax(-1) @ v
+
+
+def coord_gates(kind, sd, p, x, args):
+    """oracle.fce_oracle's bicoordcrossatt / coordatt / coordcrossatt restated to also return what the kernels keep in
+    their workspace: (x_h [N,C,H], x_w [N,C,W], g1 [N,oup,H], g2 [N,oup,W] or None, out).  g1 / g2 are the pre-sigmoid
+    gate logits of BiCoordCrossAtt, the sigmoid gates a_h / a_w of CoordAtt, and the sigmoid row gate of CoordCrossAtt
+    (no g2).  Same operations in the same order as the oracle, so `out` equals the oracle's output bit for bit
+    (test_gate_oracle_is_the_oracle)."""
+    n, c, h, w = x.shape
+    x_h = x.mean(3, keepdim=True)
+    if kind == "Bi":
+        inp, oup, reduction, heads = args
+        dh = max(8, inp // reduction) // heads
+        mid, scale = dh * heads, dh**-0.5
+        x_w = x.mean(2, keepdim=True)
+        q_h = O.conv2d(sd, p + ".proj_q_h", x_h).view(n, heads, dh, h).permute(0, 1, 3, 2)
+        k_h = O.conv2d(sd, p + ".proj_k_h", x_w).view(n, heads, dh, w)
+        v_h = O.conv2d(sd, p + ".proj_v_h", x_w).view(n, heads, dh, w).permute(0, 1, 3, 2)
+        g1 = O.conv2d(sd, p + ".out_h", _axial(q_h, k_h, v_h, scale).permute(0, 1, 3, 2).reshape(n, mid, h, 1))
+        q_w = O.conv2d(sd, p + ".proj_q_w", x_w).view(n, heads, dh, w).permute(0, 1, 3, 2)
+        k_w = O.conv2d(sd, p + ".proj_k_w", x_h).view(n, heads, dh, h)
+        v_w = O.conv2d(sd, p + ".proj_v_w", x_h).view(n, heads, dh, h).permute(0, 1, 3, 2)
+        g2 = O.conv2d(sd, p + ".out_w", _axial(q_w, k_w, v_w, scale).permute(0, 1, 3, 2).reshape(n, mid, 1, w))
+        ident = O.conv2d(sd, p + ".identity", x) if inp != oup else x
+        return x_h[..., 0], x_w[:, :, 0], g1[..., 0], g2[:, :, 0], ident * torch.sigmoid(g1 + g2)
+    x_w = x.mean(2, keepdim=True).permute(0, 1, 3, 2)
+    if kind == "Att":
+        inp, oup, _ = args
+        y = O.conv(sd, p + ".cv1", torch.cat([x_h, x_w], dim=2))
+        y_h, y_w = torch.split(y, [h, w], dim=2)
+        a_h = O.conv2d(sd, p + ".cv_h", y_h).sigmoid()
+        a_w = O.conv2d(sd, p + ".cv_w", y_w.permute(0, 1, 3, 2)).sigmoid()
+        ident = O.conv2d(sd, p + ".identity", x) if inp != oup else x
+        return x_h[..., 0], x_w[..., 0], a_h[..., 0], a_w[:, :, 0], ident * a_h * a_w
+    inp, oup, reduction, heads = args
+    mip = max(8, inp // reduction)
+    scale = (mip // heads) ** -0.5
+    y = O.conv2d(sd, p + ".cv1", torch.cat([x_h, x_w], dim=2))
+    y_h, y_w = torch.split(y, [h, w], dim=2)
+    q = O.conv2d(sd, p + ".q_conv", y_h).view(n, heads, -1, h).permute(0, 1, 3, 2)
+    k = O.conv2d(sd, p + ".k_conv", y_w).view(n, heads, -1, w)
+    v = O.conv2d(sd, p + ".v_conv", y_w).view(n, heads, -1, w).permute(0, 1, 3, 2)
+    z = _axial(q, k, v, scale).permute(0, 1, 3, 2).contiguous().view(n, mip, h, 1)
+    g1 = O.conv2d(sd, p + ".proj", z).sigmoid()
+    return x_h[..., 0], x_w[..., 0], g1[..., 0], None, x * g1
+
+
+def coord_oracle(kind, args, mod, x, dtype=torch.float64):
+    """coord_gates on the module's weights (BN folded as the oracle folds it) in `dtype`."""
+    sd = O.cast_sd(O.fuse_state_dict({"m." + k: v.cpu() for k, v in mod.state_dict().items()}), dtype)
+    with torch.no_grad():
+        return coord_gates(kind, sd, "m", x.cpu().to(dtype), list(args))
