@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "mfma_stage.h"
+#include "ops.h"
 
 namespace fce {
 

@@ -49,7 +49,7 @@ struct LaunchProbe {
   hipEvent_t* ev;  // 2 * cap events
   int cap, n;      // pairs available / used
 };
-LaunchProbe*& probe_slot();  // thread-local slot (api.hip)
+LaunchProbe*& probe_slot();  // thread-local slot (api.hip), set by fce_net_profile (net_run.hip)
 
 #define FCE_LAUNCH(K, G, B, SH, S, ...)                                                            \
   do {                                                                                             \

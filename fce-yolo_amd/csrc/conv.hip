@@ -17,6 +17,7 @@
 //   weight fragments are pre-packed in exactly this lane order (1 KiB per fragment).
 //   D: lane l holds px = l&15, couts 4(l>>4)+0..3  -> 8-byte NHWC stores.
 #include "conv_variant.h"
+#include "ops.h"
 
 namespace fce {
 

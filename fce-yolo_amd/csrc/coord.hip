@@ -12,14 +12,12 @@
 //   4. apply:   y = id(x) * gate, one vectorised 16-byte NHWC pass (id = optional 1x1 conv into y first)
 // Everything is deterministic (fixed reduction orders, no atomics).
 #include "common.h"
+#include "ops.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace fce {
-
-int conv2d(const fce_conv_desc& d, const fce_tensor& x, const void* w, const float* bias, const fce_tensor* res,
-           const fce_tensor& y, hipStream_t s, int tile = -1, const fce_tensor* dup = nullptr, int duplo = 0);
 
 enum { ACT_NONE_ = 0, ACT_SILU_ = 1, ACT_SIGMOID_ = 2 };
 

@@ -6,6 +6,7 @@
 // All in fp32 from fp32 logits (Q11: an fp16 decode cannot meet the 1e-3 tolerance).
 // Output (N, 4+nc, A) fp32, anchors ordered level-major then row-major, like torch.cat in _inference.
 #include "common.h"
+#include "ops.h"
 
 namespace fce {
 

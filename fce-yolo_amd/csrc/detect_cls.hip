@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "mfma_stage.h"
+#include "ops.h"
 
 namespace fce {
 

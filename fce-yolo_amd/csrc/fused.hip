@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "mfma_stage.h"
+#include "ops.h"
 
 namespace fce {
 

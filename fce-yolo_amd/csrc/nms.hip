@@ -21,6 +21,7 @@
 //          before the end of the sorted list, and nothing past its stop point is ever tested.
 //      Degenerate boxes (or max_det > 1024) take the literal per-box loop with the early exit.
 #include "common.h"
+#include "ops.h"
 
 #pragma clang fp contract(off)
 

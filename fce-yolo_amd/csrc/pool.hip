@@ -6,6 +6,7 @@
 // in-range element of the larger window is reachable through an in-range intermediate), so all
 // three outputs come from one read of x and are written straight into the concat buffer slices.
 #include "common.h"
+#include "ops.h"
 
 namespace fce {
 

@@ -22,6 +22,7 @@
 // cv2 is not importable here, so this restatement is pinned only by its identity / pure-padding cases
 // (DESIGN.md "Preprocessing"); the letterbox geometry is pinned by the reference's own LetterBox.
 #include "common.h"
+#include "ops.h"
 
 namespace fce {
 

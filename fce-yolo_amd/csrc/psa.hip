@@ -16,6 +16,7 @@
 //                             the A operand V^T is read from an LDS transpose of the V tile in that
 //                             same key order (two 8-byte LDS reads per fragment)
 #include "common.h"
+#include "ops.h"
 
 namespace fce {
 

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "mfma_stage.h"
+#include "ops.h"
 
 namespace fce {
 

@@ -171,18 +171,22 @@ def test_end_to_end_parity(key, e2e_fx, device):
 
 
 def test_graph_eager_and_module_forward_agree_bitwise(e2e_fx, device, monkeypatch):
-    """Captured hipGraph, direct launches (1 and 4 streams over the op DAG) and the module forward."""
+    """Captured hipGraph, direct launches (1 stream, and 2, 3, 4 and 8 streams over the op DAG) and the module
+    forward."""
     key = "yolo11n-fce_160_b2"
     fx = e2e_fx.group(key)
     model, eng, x, yg = _engine_run(key, fx, device, graph=True)
     ye = eng(x.to(device).half(), graph=False).clone()
     yg2 = eng(x.to(device).half(), graph=True).clone()  # replay
-    monkeypatch.setenv("FCE_STREAMS", "4")
-    ys = eng(x.to(device).half(), graph=False).clone()
+    ys = {}
+    for n in (4, 2, 3, 8):
+        monkeypatch.setenv("FCE_STREAMS", str(n))
+        ys[n] = eng(x.to(device).half(), graph=False).clone()
     monkeypatch.delenv("FCE_STREAMS")
     ym, _ = model(x.to(device).half())
     torch.cuda.synchronize()
-    assert torch.equal(yg, ye) and torch.equal(yg, yg2) and torch.equal(yg, ym) and torch.equal(yg, ys)
+    assert torch.equal(yg, ye) and torch.equal(yg, yg2) and torch.equal(yg, ym) and torch.equal(yg, ys[4])
+    assert all(torch.equal(yg, y) for y in ys.values()), [n for n, y in ys.items() if not torch.equal(yg, y)]
 
 
 def _predict_once(model, x):
@@ -1618,6 +1622,47 @@ def test_net_op_variant_lists_match_golden(device, monkeypatch):
     assert len(want) > 50 and set(got) == set(want)
     bad = [(i, [hex(c) for c in got[i]], [hex(c) for c in want[i]]) for i in want if got[i] != want[i]]
     assert not bad, bad[:3]
+
+
+def _golden_net_ops(monkeypatch):
+    """tests/golden/make_golden_net_ops.py as a module and its fixture, with every switch the plan reads unset."""
+    import importlib.util
+    import json
+
+    from conftest import GOLDEN
+
+    spec = importlib.util.spec_from_file_location("make_golden_net_ops", GOLDEN / "make_golden_net_ops.py")
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    for knob in (*G.FUSE_KNOBS, "FCE_TILE3AL", "FCE_WIDE3", "FCE_RING32", "FCE_NO_GEMM3", "FCE_NO_DRING"):
+        monkeypatch.delenv(knob, raising=False)
+    return G, json.loads(G.FIXTURE.read_text())
+
+
+@pytest.mark.parametrize("size", [160, 224, 704])
+@pytest.mark.parametrize("cfg", ["yolo11n-fce.yaml", "yolo11s-bifpn.yaml"])
+def test_planned_net_ops_match_golden(cfg, size, device, monkeypatch):
+    """The n and s scales at batch 2, planned without autotuning at 160, 224 and 704 (wider than the fused stem pair is
+    built for; the Bottleneck chains fit at some of these widths only), give exactly the recorded plan: per op (name,
+    bytes, flops, alt_form, skipped, variant, variants list), bytes and flops to the last bit (sums of integer-valued
+    terms; bytes of the pw2_fused ops also pins h_store), and the same ops refuse their fused form (alt_locked)."""
+    G, rec = _golden_net_ops(monkeypatch)
+    assert cfg in G.PLAN_CONFIGS and size in G.PLAN_SIZES and G.PLAN_BATCH == 2
+    want = rec["plans"][cfg][str(size)]
+    ops, locked = G.plan_ops(cases.seeded_model(cfg, 0).to(device), size, device)
+    want_ops = [[rec["names"][op[0]], *op[1:6], rec["lists"][op[6]]] for op in want["ops"]]
+    assert len(ops) == len(want_ops) > 90
+    bad = [(i, g, w) for i, (g, w) in enumerate(zip(ops, want_ops)) if g != w]
+    assert not bad, (len(bad), bad[:3])
+    assert locked == want["locked"] and (2 in locked) == (size == 704)
+
+
+def test_autotune_log_sequence_matches_golden(device, monkeypatch):
+    """The autotuned plan of yolo11n-fce at 160x160, batch 2, times the recorded (op, code) sequence: every candidate
+    of every tunable conv in op order, then 0xF00 / 0xF01 for each unlocked alternative (the times are not compared)."""
+    G, rec = _golden_net_ops(monkeypatch)
+    got = G.tune_codes(cases.seeded_model(G.TUNE[0], 0).to(device), G.TUNE[1], device)
+    assert len(rec["tune"]) > 1000 and got == rec["tune"]
 
 
 @pytest.mark.parametrize("hw", [(20, 23), (9, 7), (16, 16), (33, 20)])

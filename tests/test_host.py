@@ -329,6 +329,33 @@ def _lowered(cfg, monkeypatch, **env):
         be.close()
 
 
+def _golden_net_ops():
+    """tests/golden/make_golden_net_ops.py as a module: the configs, the env sets and the child-process runner."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("make_golden_net_ops", ROOT / "tests" / "golden" / "make_golden_net_ops.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_lowered_op_lists_match_golden():
+    """The n, s, l and m-h8 scales lowered into a NetBackend on the CPU record exactly the ops of the fixture, element
+    for element: (fce_net_op_info name, fce_net_alt_form, fce_net_c3k2_form, fce_net_op_skipped) per op, with the
+    default switches, with all five FCE_FUSE_* at 0 and with FCE_FUSE_C3K2=0 alone, each in a fresh child process."""
+    G = _golden_net_ops()
+    rec = json.loads(G.FIXTURE.read_text())
+    assert set(rec["host"]) == set(G.ENV_SETS)
+    for env in G.ENV_SETS:
+        got = G.child_host(env)
+        assert list(got) == list(G.HOST_CONFIGS) == list(rec["host"][env]), env
+        for cfg, ops in got.items():
+            want = [[rec["names"][op[0]], *op[1:]] for op in rec["host"][env][cfg]]
+            assert len(ops) == len(want) > 90, (env, cfg, len(ops), len(want))
+            bad = [(i, g, w) for i, (g, w) in enumerate(zip(ops, want)) if g != w]
+            assert not bad, (env, cfg, len(bad), bad[:3])
+
+
 def test_lowering_records_the_fused_alternatives(monkeypatch):
     """Graph lowering (no GPU): the n scale records the one-kernel stem pair after its two convs, the fused C3k2 after
     each qualifying block's four convs, and per Detect level P3 / P4 the box tail before the cls chain, whose five ops
