@@ -9,7 +9,17 @@ Layout:
   modules.py  drop-in nn.Modules named and shaped like the reference's
   parser.py   the reference YAML parser restated (builds our modules)
   engine.py   whole-graph lowering to the native executor (hipGraph replay) + NMS
+  tta.py      test-time augmentation: AugmentedEngine (three passes, one merged prediction)
   weights.py  portable seeded weights
 """
 
 __version__ = "0.1.0"
+__all__ = ["AugmentedEngine"]
+
+
+def __getattr__(name):
+    if name == "AugmentedEngine":  # resolved on first use: importing the package stays free of torch
+        from .tta import AugmentedEngine
+
+        return AugmentedEngine
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -157,6 +157,21 @@ class NmsOpts(C.Structure):
     ]
 
 
+class TtaPart(C.Structure):
+    """fce_tta_part: anchors [first, first + count) of one pass of the augmented forward."""
+    _fields_ = [
+        ("pred", C.c_void_p),
+        ("best", C.c_void_p),
+        ("anchors", C.c_int),
+        ("first", C.c_int),
+        ("count", C.c_int),
+        ("scale", C.c_float),
+        ("flip", C.c_int),
+        ("img_h", C.c_int),
+        ("img_w", C.c_int),
+    ]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _SZ = C.c_size_t
@@ -216,6 +231,8 @@ _SIGS = {
     "fce_nms_best": (_I, [_P, _P, _I, _I, _I, C.c_float, C.c_float, _I, _I, C.c_float, _P, _SZ, _P, _P, _P, _P]),
     "fce_nms_workspace_bytes_ex": (_SZ, [_I, _I, _I, C.POINTER(NmsOpts)]),
     "fce_nms_ex": (_I, [_P, _P, _I, _I, _I, C.POINTER(NmsOpts), _P, _SZ, _P, _P, _P, _P]),
+    "fce_tta_scale_img": (_I, [_PT, _PT, _I, _I, _I, C.c_float, _P]),
+    "fce_tta_merge": (_I, [C.POINTER(TtaPart), _I, _I, _I, _P, _P, _P]),
     "fce_copy": (_I, [_PT, _PT, _P]),
     "fce_net_create": (_P, []),
     "fce_net_destroy": (None, [_P]),

@@ -165,6 +165,15 @@ int fce_scale_boxes(float* dets, const int32_t* counts, int n, int max_det, cons
                     void* stream) {
   FCE_GUARD(return scale_boxes(dets, counts, n, max_det, params, S(stream));)
 }
+int fce_tta_scale_img(const fce_tensor* x, const fce_tensor* y, int flip, int h_s, int w_s, float pad_value,
+                      void* stream) {
+  FCE_CHECK(x && y, "fce_tta_scale_img: null argument");
+  FCE_GUARD(return tta_scale_img(*x, *y, flip, h_s, w_s, pad_value, S(stream));)
+}
+int fce_tta_merge(const fce_tta_part* parts, int nparts, int batch, int rows, float* pred, unsigned long long* best,
+                  void* stream) {
+  FCE_GUARD(return tta_merge(parts, nparts, batch, rows, pred, best, S(stream));)
+}
 int fce_copy(const fce_tensor* src, const fce_tensor* dst, void* stream) {
   FCE_CHECK(src && dst, "fce_copy: null argument");
   FCE_GUARD(return copy(*src, *dst, S(stream));)

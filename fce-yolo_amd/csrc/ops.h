@@ -60,6 +60,10 @@ int pw2_fused(const fce_pw2_desc& d, const fce_tensor& x1, const fce_tensor* r1,
 // preprocess.hip
 int letterbox(const fce_letterbox_img* imgs, int n, uint8_t* dst, int H, int W, int pad, hipStream_t s);
 int scale_boxes(float* dets, const int32_t* counts, int n, int max_det, const fce_box_scale* sc, hipStream_t s);
+// tta.hip
+int tta_scale_img(const fce_tensor& x, const fce_tensor& y, int flip, int hs, int ws, float pad, hipStream_t s);
+int tta_merge(const fce_tta_part* parts, int nparts, int batch, int rows, float* pred, unsigned long long* best,
+              hipStream_t s);
 
 }  // namespace fce
 

@@ -5,7 +5,8 @@ nn/autobackend.py:667-700 AutoBackend.forward) calls `self.model(im)` on a prepr
 batch and hands the result to models/yolo/detect/predict.py postprocess (NMS + scale_boxes).  With
 `patch_autobackend(predictor.model)` that call runs this package's whole-graph Engine on the MI355X
 (one plan per input shape, direct launches), returning the same (B, 4+nc, A) prediction tensor, so
-the reference's postprocess, Results and plotting stay untouched.  `device_postprocess(predictor)` in
+the reference's postprocess, Results and plotting stay untouched; `augment=True` runs the three-pass
+`tta.AugmentedEngine` (nn/tasks.py:422-484) and returns its merged tensor.  `device_postprocess(predictor)` in
 addition swaps its NMS for the device NMS (bit-exact with TorchNMS).
 
 Both take objects of the reference package but import nothing from it.
@@ -19,6 +20,7 @@ import torch
 
 from .engine import Engine, non_max_suppression
 from .parser import DetectionModel
+from .tta import AugmentedEngine
 
 
 def from_reference_model(ref_model, device=None) -> DetectionModel:
@@ -41,14 +43,16 @@ def patch_autobackend(backend, device=None):
     if dev.type != "cuda":
         raise RuntimeError("patch_autobackend: fce_yolo_amd runs on ROCm devices only; no CPU fallback")
     model = from_reference_model(backend.model, dev)
-    engines: dict[tuple, Engine] = {}
+    engines: dict[tuple, Engine | AugmentedEngine] = {}
 
     def forward(self, im, augment=False, visualize=False, embed=None, **kwargs):
-        if augment or visualize or embed:
-            raise NotImplementedError("fce_yolo_amd: augment / visualize / embed are not on the inference path")
+        if visualize or embed:
+            raise NotImplementedError("fce_yolo_amd: visualize / embed are not on the inference path")
         key = (im.shape[0], im.shape[2], im.shape[3])
+        if augment:  # tasks.py:422-444 _predict_augment: three passes merged along the anchor axis
+            key += ("augment",)
         if key not in engines:
-            engines[key] = Engine(model, im.shape[0], (im.shape[2], im.shape[3]), dev)
+            engines[key] = (AugmentedEngine if augment else Engine)(model, im.shape[0], (im.shape[2], im.shape[3]), dev)
         return engines[key](im.contiguous())
 
     backend.forward = types.MethodType(forward, backend)

@@ -163,7 +163,7 @@ class Predictor:
 
     def __init__(self, model, batch: int, imgsz=640, device=None, conf=0.25, iou=0.7, max_det=300,
                  lanes: int | None = None, graph: bool = True, workers: int | None = None, copy_stream: bool = True,
-                 gather=None):
+                 gather=None, augment: bool = False):
         """`lanes`: batches on the device at once; default by scale (`default_lanes`): 5 on the n / s scales
         (measured best for 32 x 480x640 images, scripts/predict_diag.py), 3 on m / l, where every lane's
         activation arena is large and more than three arenas overflow the MALL (bench.default_lanes).
@@ -172,13 +172,20 @@ class Predictor:
         (18.9k against 15.9k images/s with the copy on the lane's own stream, scripts/predict_diag.py).
         `gather` (a `dist.DeviceGather`, set by dist.ShardedHostPredictor): every batch's packed NMS outputs are
         all-gathered over the ranks on one side stream in batch order before the D2H copy, and results are the
-        whole global batch's (every submit must then carry exactly `batch` images)."""
+        whole global batch's (every submit must then carry exactly `batch` images).
+        `augment`: the reference's predict(augment=True): every lane's executor is a `tta.AugmentedEngine` (three
+        passes merged along the anchor axis, nn/tasks.py:422-484) and its NMS runs over the merged anchors."""
         import os
         from concurrent.futures import ThreadPoolExecutor
 
         if lanes is None:
             lanes = default_lanes(model)
-        self.engine = Engine(model, batch, imgsz, device, graph=graph)
+        if augment:
+            from .tta import AugmentedEngine
+
+            self.engine = AugmentedEngine(model, batch, imgsz, device, graph=graph)
+        else:
+            self.engine = Engine(model, batch, imgsz, device, graph=graph)
         self.device = self.engine.device
         self.batch = batch
         self.max_det = max_det

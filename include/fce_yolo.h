@@ -22,6 +22,8 @@
  *   fce_detect_decode     nn/modules/head.py:149-167 Detect._inference, block.py:76-79 DFL,
  *                         utils/tal.py:352-376 make_anchors / dist2bbox
  *   fce_nms               utils/nms.py:13-166 non_max_suppression + :239-296 TorchNMS.nms
+ *   fce_tta_scale_img     utils/torch_utils.py:476-495 scale_img (+ the flip of nn/tasks.py:439)
+ *   fce_tta_merge         nn/tasks.py:446-484 _descale_pred, _clip_augmented (+ the torch.cat of :444)
  *   fce_copy              the NCHW <-> NHWC / fp32 <-> fp16 edges a drop-in module needs
  *   fce_net_*             nn/tasks.py:160-188 BaseModel._predict_once (graph executor) and
  *                         nn/autobackend.py:667-700 / :912-926 (forward, warmup) in hipGraph form
@@ -144,6 +146,32 @@ typedef struct fce_box_scale {
   int pad_x, pad_y, h0, w0;
 } fce_box_scale;
 int fce_scale_boxes(float* dets, const int32_t* counts, int n, int max_det, const fce_box_scale* params, void* stream);
+
+/* ---------------------------------------------------------------- test-time augmentation */
+/* utils/torch_utils.py:476-495 scale_img with the x.flip(fi) of nn/tasks.py:439 folded in: x NCHW f16 / f32 / u8
+ * (u8 read as fp16(v / 255), as the stem reads it) is flipped (0 none, 2 up-down, 3 left-right: the reference's
+ * codes), resized to (h_s, w_s) by ATen's bilinear rule (align_corners = False, explicit size; fp32 arithmetic on the
+ * fp16-rounded source, rounded once to fp16) and padded right / bottom with pad_value (the reference's 0.447) into y,
+ * the NCHW f16 canvas of the scaled pass (same n and c).  h_s == x->h and w_s == x->w gives the converted copy. */
+int fce_tta_scale_img(const fce_tensor* x, const fce_tensor* y, int flip, int h_s, int w_s, float pad_value,
+                      void* stream);
+/* One pass of nn/tasks.py:422-444 DetectionModel._predict_augment: anchors [first, first + count) of its
+ * (batch, rows, anchors) fp32 prediction and (batch, anchors) best-class keys (NULL: none). */
+typedef struct fce_tta_part {
+  const float* pred;
+  const unsigned long long* best;
+  int anchors, first, count;
+  float scale;          /* the pass's image scale: rows 0..3 are divided by it */
+  int flip;             /* 0 none, 2 up-down (cy = img_h - cy), 3 left-right (cx = img_w - cx) */
+  int img_h, img_w;     /* the unscaled image */
+} fce_tta_part;
+/* nn/tasks.py:446-466 _descale_pred, :468-484 _clip_augmented and the torch.cat of :444 in one launch: pred
+ * (batch, rows, sum count) fp32 = the parts' anchor ranges side by side, rows 0..3 (cx, cy, w, h) as p / scale (an
+ * fp32 division) and mirrored for a flipped pass, the other rows copied; best (nullable; then every part has keys):
+ * the keys copied (they hold score and class only).  1..4 parts, passed by value to the kernel: nothing is read from
+ * a descriptor in memory.  Scale 1 without a flip reproduces the source bits. */
+int fce_tta_merge(const fce_tta_part* parts, int nparts, int batch, int rows, float* pred, unsigned long long* best,
+                  void* stream);
 
 /* ---------------------------------------------------------------- pooling / fusion */
 /* SPPF chain: y1 = maxpool_k(x), y2 = maxpool_k(y1), y3 = maxpool_k(y2), stride 1, -inf pad. */
