@@ -10,11 +10,13 @@ Layout:
   parser.py   the reference YAML parser restated (builds our modules)
   engine.py   whole-graph lowering to the native executor (hipGraph replay) + NMS
   tta.py      test-time augmentation: AugmentedEngine (three passes, one merged prediction)
+  val.py      validation: Validator (forward, NMS and GT matching on the device), DeviceMatcher
+  metrics.py  AP / precision / recall from the matched detections (numpy, host)
   weights.py  portable seeded weights
 """
 
 __version__ = "0.1.0"
-__all__ = ["AugmentedEngine"]
+__all__ = ["AugmentedEngine", "Validator"]
 
 
 def __getattr__(name):
@@ -22,4 +24,8 @@ def __getattr__(name):
         from .tta import AugmentedEngine
 
         return AugmentedEngine
+    if name == "Validator":
+        from .val import Validator
+
+        return Validator
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -174,6 +174,15 @@ int fce_tta_merge(const fce_tta_part* parts, int nparts, int batch, int rows, fl
                   void* stream) {
   FCE_GUARD(return tta_merge(parts, nparts, batch, rows, pred, best, S(stream));)
 }
+size_t fce_val_match_workspace_bytes(int n, int max_det, int max_gt_total, int niou) {
+  return val_match_ws_bytes(n, max_det, max_gt_total, niou);
+}
+int fce_val_match(const float* dets, const int32_t* counts, int n, int max_det, const float* gt_boxes,
+                  const float* gt_cls, const int32_t* gt_off, const float* iouv, int niou, void* ws, size_t ws_bytes,
+                  uint16_t* tp, void* stream) {
+  FCE_GUARD(return val_match(dets, counts, n, max_det, gt_boxes, gt_cls, gt_off, iouv, niou, ws, ws_bytes, tp,
+                             S(stream));)
+}
 int fce_copy(const fce_tensor* src, const fce_tensor* dst, void* stream) {
   FCE_CHECK(src && dst, "fce_copy: null argument");
   FCE_GUARD(return copy(*src, *dst, S(stream));)

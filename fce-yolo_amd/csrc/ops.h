@@ -64,6 +64,11 @@ int scale_boxes(float* dets, const int32_t* counts, int n, int max_det, const fc
 int tta_scale_img(const fce_tensor& x, const fce_tensor& y, int flip, int hs, int ws, float pad, hipStream_t s);
 int tta_merge(const fce_tta_part* parts, int nparts, int batch, int rows, float* pred, unsigned long long* best,
               hipStream_t s);
+// val.hip
+size_t val_match_ws_bytes(int n, int max_det, int max_gt_total, int niou);
+int val_match(const float* dets, const int32_t* counts, int n, int max_det, const float* gt_boxes, const float* gt_cls,
+              const int32_t* gt_off, const float* iouv, int niou, void* ws, size_t ws_bytes, uint16_t* tp,
+              hipStream_t s);
 
 }  // namespace fce
 

@@ -335,13 +335,16 @@ class Pipeline:
     """
 
     def __init__(self, engine: Engine, depth: int = 2, post=None, defer: bool = True, lanes: int = 1,
-                 post_every: int = 1, layout_batch: int | None = None, **nms_kw):
+                 post_every: int = 1, layout_batch: int | None = None, slot_tail: int = 0, **nms_kw):
         """`post(k0, m)`, if given, runs on a side stream after the NMS of slots k0 .. k0 + m - 1 (e.g. the multi-GPU
         gather of their outputs, dist.ShardedPredictor); those slots' NMS outputs are reused only after it too has
         finished.  `post_every` = G (lanes only): one post per G consecutive batches, whose NMS outputs are then one
         contiguous block (`outbuf[k0 * nb : (k0 + m) * nb]`, nb = NMS.packed_bytes(layout_batch)), so a gather is one
         collective per G batches; `flush()` posts a partial group.  `layout_batch`: NMS outputs laid out for that
-        many images (the largest shard of a sharded batch)."""
+        many images (the largest shard of a sharded batch).  `slot_tail`: bytes appended to every slot's packed NMS
+        outputs (`slot_block(k)[nb:]`) for what a caller computes from them on the slot's stream (`slot_stream(k)`),
+        so both leave the device in one copy (val.Validator's true-positive words); not with `post` groups, whose
+        blocks are contiguous NMS outputs."""
         self.lanes = max(1, int(lanes))
         self.G = max(1, int(post_every)) if (post is not None and self.lanes > 1) else 1
         unit = self.lanes * self.G // math.gcd(self.lanes, self.G)
@@ -359,8 +362,10 @@ class Pipeline:
         self.bests = [engine.new_best() for _ in range(depth)]
         lb = engine.batch if layout_batch is None else int(layout_batch)
         self.nb = NMS.packed_bytes(lb, nms_kw.get("max_det", 300))
-        self.outbuf = torch.zeros(depth * self.nb, dtype=torch.uint8, device=dev)  # slot k: [k nb, (k + 1) nb)
-        self.nms = [NMS(engine.batch, engine.anchors, engine.nc, dev, buf=self.outbuf[k * self.nb:(k + 1) * self.nb],
+        assert slot_tail >= 0 and slot_tail % 16 == 0 and (slot_tail == 0 or post is None)
+        self.slot_bytes = self.nb + slot_tail  # slot k: [k slot_bytes, k slot_bytes + nb) NMS outputs, then the tail
+        self.outbuf = torch.zeros(depth * self.slot_bytes, dtype=torch.uint8, device=dev)
+        self.nms = [NMS(engine.batch, engine.anchors, engine.nc, dev, buf=self.slot_block(k)[:self.nb],
                         layout_batch=lb, **nms_kw) for k in range(depth)]
         self.side = torch.cuda.Stream(dev)
         self.fwd_done = [torch.cuda.Event() for _ in range(depth)]
@@ -385,6 +390,15 @@ class Pipeline:
         self._groups = {}  # slot -> (first slot, slots) of the group it was last posted with
         if defer:
             N.call("fce_net_set_fork", engine.net, N.lib().fce_net_fork_hint(engine.net))
+
+    def slot_block(self, k: int) -> torch.Tensor:
+        """Slot k's bytes of `outbuf`: its packed NMS outputs (nb bytes), then its `slot_tail`."""
+        return self.outbuf[k * self.slot_bytes:(k + 1) * self.slot_bytes]
+
+    def slot_stream(self, k: int) -> torch.cuda.Stream:
+        """The stream slot k's NMS runs on: work issued on it after `submit` returned slot k follows that NMS and
+        precedes the slot's next one (a lane's stream; without lanes the NMS side stream)."""
+        return self.lane_streams[k % self.lanes] if self.lanes > 1 else self.side
 
     def _issue_nms(self, k: int, fork: bool):
         self.side.wait_event(self.fwd_done[k])

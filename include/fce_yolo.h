@@ -24,6 +24,8 @@
  *   fce_nms               utils/nms.py:13-166 non_max_suppression + :239-296 TorchNMS.nms
  *   fce_tta_scale_img     utils/torch_utils.py:476-495 scale_img (+ the flip of nn/tasks.py:439)
  *   fce_tta_merge         nn/tasks.py:446-484 _descale_pred, _clip_augmented (+ the torch.cat of :444)
+ *   fce_val_match         models/yolo/detect/val.py:274-288 _process_batch: utils/metrics.py:57-77 box_iou +
+ *                         engine/validator.py:266-306 BaseValidator.match_predictions
  *   fce_copy              the NCHW <-> NHWC / fp32 <-> fp16 edges a drop-in module needs
  *   fce_net_*             nn/tasks.py:160-188 BaseModel._predict_once (graph executor) and
  *                         nn/autobackend.py:667-700 / :912-926 (forward, warmup) in hipGraph form
@@ -330,6 +332,25 @@ typedef struct fce_nms_opts {
 size_t fce_nms_workspace_bytes_ex(int n, int nc, int anchors, const fce_nms_opts* o);
 int fce_nms_ex(const float* pred, const unsigned long long* best, int n, int nc, int anchors, const fce_nms_opts* o,
                void* ws, size_t ws_bytes, float* dets, int64_t* keep, int32_t* counts, void* stream);
+
+/* ---------------------------------------------------------------- validation */
+/* models/yolo/detect/val.py:274-288 _process_batch on the device: utils/metrics.py:57-77 box_iou (the reference's fp32
+ * arithmetic in its order, IEEE division) masked by class equality, then engine/validator.py:266-306
+ * match_predictions (the numpy variant) for every threshold, as one launch per batch with one workgroup per image:
+ *   g*(d) = arg max_g iou[g, d],  m(d) = max_g iou[g, d]
+ *   bit i of tp[b, d] = m(d) >= iouv[i] and no d' < d has g*(d') == g*(d) and m(d') >= iouv[i]
+ * which is the reference's result in every cell.  Of exactly equal IoUs of one detection the higher GT index wins
+ * (the reference's order there is numpy's unstable sort: undefined beyond 16 matches, this rule up to 16).
+ * dets / counts: the NMS outputs (n, max_det, 6) / (n), boxes in the frame of gt_boxes; image b owns GT rows
+ * [gt_off[b], gt_off[b + 1]) of gt_boxes (M, 4) xyxy and gt_cls (M) (device memory, read as given: the caller
+ * keeps gt_off ascending and within M).  iouv: niou (1..16) thresholds in HOST memory, passed to the kernel by value.
+ * tp (n, max_det) uint16: every row is written, rows >= counts[b] as 0.  The workspace is 0 bytes up to 512
+ * detections per image (the state stays in LDS) and 8 bytes per detection slot beyond; nothing is allocated and
+ * nothing synchronises, so the call can be captured into a hipGraph like the NMS it follows. */
+size_t fce_val_match_workspace_bytes(int n, int max_det, int max_gt_total, int niou);
+int fce_val_match(const float* dets, const int32_t* counts, int n, int max_det, const float* gt_boxes,
+                  const float* gt_cls, const int32_t* gt_off, const float* iouv, int niou, void* ws, size_t ws_bytes,
+                  uint16_t* tp, void* stream);
 
 /* ---------------------------------------------------------------- layout / dtype edges */
 /* dst = src with layout / dtype conversion (same n,c,h,w). */
