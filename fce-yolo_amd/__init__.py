@@ -10,13 +10,14 @@ Layout:
   parser.py   the reference YAML parser restated (builds our modules)
   engine.py   whole-graph lowering to the native executor (hipGraph replay) + NMS
   tta.py      test-time augmentation: AugmentedEngine (three passes, one merged prediction)
-  val.py      validation: Validator (forward, NMS and GT matching on the device), DeviceMatcher
-  metrics.py  AP / precision / recall from the matched detections (numpy, host)
+  val.py      validation: Validator (forward, NMS, GT matching and the confusion matrix on the device),
+              DeviceMatcher, DeviceConfusionMatrix
+  metrics.py  AP / precision / recall from the matched detections, ConfusionMatrix (numpy, host)
   weights.py  portable seeded weights
 """
 
 __version__ = "0.1.0"
-__all__ = ["AugmentedEngine", "Validator"]
+__all__ = ["AugmentedEngine", "ConfusionMatrix", "Validator"]
 
 
 def __getattr__(name):
@@ -28,4 +29,8 @@ def __getattr__(name):
         from .val import Validator
 
         return Validator
+    if name == "ConfusionMatrix":
+        from .metrics import ConfusionMatrix
+
+        return ConfusionMatrix
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

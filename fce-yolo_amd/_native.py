@@ -235,6 +235,8 @@ _SIGS = {
     "fce_tta_merge": (_I, [C.POINTER(TtaPart), _I, _I, _I, _P, _P, _P]),
     "fce_val_match_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "fce_val_match": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _SZ, _P, _P]),
+    "fce_val_confusion_workspace_bytes": (_SZ, [_I, _I]),
+    "fce_val_confusion": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, C.c_float, C.c_float, _P, _SZ, _P, _P]),
     "fce_copy": (_I, [_PT, _PT, _P]),
     "fce_net_create": (_P, []),
     "fce_net_destroy": (None, [_P]),

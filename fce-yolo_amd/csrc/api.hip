@@ -183,6 +183,13 @@ int fce_val_match(const float* dets, const int32_t* counts, int n, int max_det, 
   FCE_GUARD(return val_match(dets, counts, n, max_det, gt_boxes, gt_cls, gt_off, iouv, niou, ws, ws_bytes, tp,
                              S(stream));)
 }
+size_t fce_val_confusion_workspace_bytes(int n, int max_det) { return val_confusion_ws_bytes(n, max_det); }
+int fce_val_confusion(const float* dets, const int32_t* counts, int n, int max_det, const float* gt_boxes,
+                      const float* gt_cls, const int32_t* gt_off, int nc, float conf, float iou_thres, void* ws,
+                      size_t ws_bytes, int32_t* matrix, void* stream) {
+  FCE_GUARD(return val_confusion(dets, counts, n, max_det, gt_boxes, gt_cls, gt_off, nc, conf, iou_thres, ws, ws_bytes,
+                                 matrix, S(stream));)
+}
 int fce_copy(const fce_tensor* src, const fce_tensor* dst, void* stream) {
   FCE_CHECK(src && dst, "fce_copy: null argument");
   FCE_GUARD(return copy(*src, *dst, S(stream));)

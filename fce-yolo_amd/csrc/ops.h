@@ -69,6 +69,10 @@ size_t val_match_ws_bytes(int n, int max_det, int max_gt_total, int niou);
 int val_match(const float* dets, const int32_t* counts, int n, int max_det, const float* gt_boxes, const float* gt_cls,
               const int32_t* gt_off, const float* iouv, int niou, void* ws, size_t ws_bytes, uint16_t* tp,
               hipStream_t s);
+size_t val_confusion_ws_bytes(int n, int max_det);
+int val_confusion(const float* dets, const int32_t* counts, int n, int max_det, const float* gt_boxes,
+                  const float* gt_cls, const int32_t* gt_off, int nc, float conf, float iou_thres, void* ws,
+                  size_t ws_bytes, int32_t* matrix, hipStream_t s);
 
 }  // namespace fce
 

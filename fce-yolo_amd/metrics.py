@@ -3,7 +3,8 @@ compute_ap / ap_per_class, :913-1076 Metric, :1079-1201 DetMetrics), numpy only.
 
 The device decides which detections are true positives at each IoU threshold (`val.DeviceMatcher`, csrc/val.hip); what
 remains is a sort by confidence and a few cumulative sums over all detections of the dataset, float64 numpy exactly as
-the reference runs it.  No plots, no confusion matrix, no COCO JSON.
+the reference runs it.  The confusion matrix is counted on the device too (`val.DeviceConfusionMatrix`) and held
+here as `ConfusionMatrix` (metrics.py:380-534).  No plots, no COCO JSON.
 """
 
 from __future__ import annotations
@@ -161,3 +162,29 @@ class DetMetrics:
         keys = [*self.keys, "fitness"]
         values = ((float(x) if hasattr(x, "item") else x) for x in ([*self.mean_results(), self.fitness]))
         return dict(zip(keys, values))
+
+
+class ConfusionMatrix:
+    """metrics.py:380-403, :524-534 and the normalisation of :585 for detection: `matrix` (nc + 1, nc + 1) float64,
+    row = predicted class, column = true class, index nc = background.  The counting itself (process_batch) runs on
+    the device (`val.DeviceConfusionMatrix`, csrc/val.hip); this object holds a run's counts."""
+
+    def __init__(self, names=(), matrix=None):
+        self.names = names
+        self.nc = len(names)
+        self.matrix = np.zeros((self.nc + 1, self.nc + 1))
+        if matrix is not None:
+            m = np.asarray(matrix)
+            if m.shape != self.matrix.shape:
+                raise ValueError(f"ConfusionMatrix: matrix must be {self.matrix.shape}, not {m.shape}")
+            self.matrix[...] = m
+
+    def tp_fp(self):
+        """metrics.py:524-534: (true positives, false positives) per class, the background dropped."""
+        tp = self.matrix.diagonal()
+        fp = self.matrix.sum(1) - tp
+        return tp[:-1], fp[:-1]
+
+    def normalized(self) -> np.ndarray:
+        """metrics.py:585: every column (true class) divided by its sum + 1e-9, as the reference's plot shows it."""
+        return self.matrix / (self.matrix.sum(0).reshape(1, -1) + 1e-9)

@@ -6,7 +6,8 @@ models/yolo/detect/val.py: preprocess, postprocess, update_metrics, get_stats):
     u8 canvases --(Engine: forward)--> pred --(fce_nms_ex: conf 0.001, multi_label)--> (k, 6) per image, canvas pixels
       --(fce_val_match: box_iou x class equality, match_predictions at the ten thresholds)--> tp words (k) uint16
       --(one D2H copy: packed NMS outputs + tp words)--> host: DetMetrics.update_stats per image
-    stats(): metrics.ap_per_class over everything accumulated -> results_dict
+      --(fce_val_confusion, beside the matcher: detections above 0.25, IoU > 0.45)--> resident (nc + 1)^2 int32 counts
+    stats(): metrics.ap_per_class over everything accumulated -> results_dict; the counts -> confusion_matrix
 
 The reference syncs once per image (`iou.cpu().numpy()`) and matches in numpy; here the matching runs beside the NMS
 on the lane's stream and the host only unpacks bits.  GT boxes are prepared on the host exactly as
@@ -26,7 +27,7 @@ import torch
 
 from . import _native as N
 from .engine import NMS, Engine, Pipeline
-from .metrics import DetMetrics
+from .metrics import ConfusionMatrix, DetMetrics
 from .predict import default_lanes
 
 GT_CHUNK = 256  # csrc/val.hip VAL_GT_CHUNK: GT boxes staged in LDS at a time
@@ -98,6 +99,62 @@ class DeviceMatcher:
         return out
 
 
+def confusion_conf(conf) -> float:
+    """utils/metrics.py:465: the confusion matrix counts detections above 0.25 when the validation default conf
+    (0.001) or None is passed, above `conf` otherwise."""
+    return 0.25 if conf in {None, 0.001} else conf
+
+
+class DeviceConfusionMatrix:
+    """`ConfusionMatrix.process_batch` (utils/metrics.py:441-518) for a whole batch on the device, accumulated in
+    one resident (nc + 1, nc + 1) int32 table (fce_val_confusion):
+
+        cm = DeviceConfusionMatrix(nc, batch, max_det, device)
+        cm(dets, counts, gt_boxes, gt_cls, gt_off, n=n)           # per batch: adds images 0..n-1, no host work
+        counts = cm.numpy()                                       # once, at the end: syncs, returns a copy
+
+    Inputs as `DeviceMatcher`; `conf` and `iou_thres` are used as given (`confusion_conf` is the reference's rule for
+    the validator's conf).  Runs on the current stream, allocates nothing per call and can be captured.  A class
+    outside 0..nc-1 is counted nowhere but in the workspace's error word; `numpy()` raises if there was one."""
+
+    def __init__(self, nc: int, batch: int, max_det: int, device, conf: float = 0.25, iou_thres: float = 0.45):
+        self.nc, self.batch, self.max_det, self.device = int(nc), batch, max_det, torch.device(device)
+        self.conf, self.iou_thres = float(conf), float(iou_thres)
+        nb = N.lib().fce_val_confusion_workspace_bytes(batch, max_det)
+        if self.nc <= 0 or nb == 0:
+            raise ValueError("DeviceConfusionMatrix: nc, batch and max_det must be positive")
+        self.ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)  # word 0: out-of-range classes met
+        self.matrix = torch.zeros((self.nc + 1, self.nc + 1), dtype=torch.int32, device=self.device)
+
+    def __call__(self, dets, counts, gt_boxes, gt_cls, gt_off, n: int | None = None) -> torch.Tensor:
+        n = self.batch if n is None else int(n)
+        if not 0 < n <= self.batch:
+            raise ValueError(f"DeviceConfusionMatrix: n must be 1..{self.batch}")
+        assert dets.is_contiguous() and dets.dtype == torch.float32 and tuple(dets.shape) == (self.batch, self.max_det, 6)
+        assert counts.is_contiguous() and counts.dtype == torch.int32 and counts.numel() == self.batch
+        assert gt_boxes.is_contiguous() and gt_boxes.dtype == torch.float32 and gt_boxes.dim() == 2 and gt_boxes.shape[1] == 4
+        assert gt_cls.is_contiguous() and gt_cls.dtype == torch.float32 and gt_cls.numel() == gt_boxes.shape[0]
+        assert gt_off.is_contiguous() and gt_off.dtype == torch.int32 and gt_off.numel() >= n + 1
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        N.call("fce_val_confusion", dets.data_ptr(), counts.data_ptr(), n, self.max_det, gt_boxes.data_ptr(),
+               gt_cls.data_ptr(), gt_off.data_ptr(), self.nc, self.conf, self.iou_thres, self.ws.data_ptr(),
+               self.ws.numel(), self.matrix.data_ptr(), stream)
+        return self.matrix
+
+    def zero_(self) -> None:
+        """Clear the matrix and the error word, in stream order on the current stream."""
+        self.matrix.zero_()
+        self.ws[:16].zero_()
+
+    def numpy(self) -> np.ndarray:
+        """The counts so far, (nc + 1, nc + 1) int32 on the host (synchronises the device)."""
+        torch.cuda.synchronize(self.device)
+        bad = int(self.ws[:4].view(torch.int32).item())
+        if bad:
+            raise N.FceError(f"fce_val_confusion: {bad} GT or detection classes outside 0..{self.nc - 1}")
+        return self.matrix.cpu().numpy().copy()
+
+
 class _Slot:
     """What one pipeline slot owns beside its NMS: the canvas of a batch that came from the host or was short, the
     GT staging (pinned host + device: gt_off | gt_cls | gt_boxes) and the pinned copy of its results."""
@@ -128,7 +185,9 @@ class Validator:
     DetectionValidator.postprocess: multi_label NMS, agnostic = single_cls or agnostic_nms).  `single_cls` zeroes the
     predicted classes as `_prepare_pred` does; the GT classes of such a dataset are already 0 (the dataset does that).
     `lanes` batches are in flight; their results are read in submission order, when a slot is needed again or at
-    `stats()`, so the accumulated statistics do not depend on `lanes`."""
+    `stats()`, so the accumulated statistics do not depend on `lanes`.  As under the reference's defaults (plots) the
+    confusion matrix is always counted: after `stats()`, `confusion_matrix` (metrics.ConfusionMatrix) holds that run's
+    counts (utils/metrics.py:441-518 at conf 0.25 when `conf` is 0.001 or None, else `conf`; IoU 0.45)."""
 
     def __init__(self, model, batch: int, imgsz=640, device=None, conf=0.001, iou=0.7, max_det=300,
                  lanes: int | None = None, graph: bool = True, single_cls: bool = False, agnostic_nms: bool = False):
@@ -146,7 +205,14 @@ class Validator:
         self.matcher = DeviceMatcher(batch, max_det, self.device)
         self.niou = self.matcher.niou
         self.slots = [_Slot(batch, self.pipe.slot_bytes) for _ in range(self.pipe.depth)]
-        self.metrics = DetMetrics(getattr(model, "names", None) or {})
+        # one table per slot: slots run on different streams, and beyond DET_LDS detections the kernel's state is in
+        # the table's workspace.  stats() adds them up (integer counts: the sum does not depend on `lanes`)
+        self.confusion = [DeviceConfusionMatrix(self.engine.nc, batch, max_det, self.device, conf=confusion_conf(conf))
+                          for _ in self.slots]
+        names = getattr(model, "names", None) or {}
+        self.cm_names = names if len(names) == self.engine.nc else {i: f"{i}" for i in range(self.engine.nc)}
+        self.confusion_matrix = ConfusionMatrix(self.cm_names)  # the last stats()'s run
+        self.metrics = DetMetrics(names)
         self.seen = 0
         self._fifo = deque()  # slots in flight, oldest first
 
@@ -169,6 +235,8 @@ class Validator:
         if img.dtype != torch.uint8 or tuple(img.shape[1:]) != (3, self.H, self.W) or not 0 < n <= self.batch:
             raise ValueError(f"Validator: img must be uint8 (1..{self.batch}, 3, {self.H}, {self.W})")
         boxes, cls, off = pack_gt(batch["batch_idx"], batch["cls"], batch["bboxes"], n, self.H, self.W)
+        if cls.numel() and not (float(cls.min()) > -1 and float(cls.max()) < self.engine.nc):  # as .int() truncates
+            raise ValueError(f"Validator: cls outside 0..{self.engine.nc - 1}")
         k = self.pipe.i % self.pipe.depth  # the slot this batch goes to
         sl = self.slots[k]
         if sl.pending is not None:  # the slot's previous batch (and every older one: submission order)
@@ -193,9 +261,11 @@ class Validator:
         with torch.cuda.stream(self.pipe.slot_stream(k)):
             if self.single_cls:
                 nms.dets[:, :, 5].zero_()  # val.py:164-165: pred["cls"] *= 0
-            self.matcher(nms.dets, nms.counts, d[o_box:o_box + 16 * max(M, 1)].view(torch.float32).view(-1, 4)[:max(M, 1)],
-                         d[o_cls:o_cls + 4 * max(M, 1)].view(torch.float32), d[:4 * (B + 1)].view(torch.int32),
+            gt = (d[o_box:o_box + 16 * max(M, 1)].view(torch.float32).view(-1, 4)[:max(M, 1)],
+                  d[o_cls:o_cls + 4 * max(M, 1)].view(torch.float32), d[:4 * (B + 1)].view(torch.int32))
+            self.matcher(nms.dets, nms.counts, *gt,
                          out=block[self.pipe.nb:self.pipe.nb + B * self.max_det * 2].view(torch.int16))
+            self.confusion[k](nms.dets, nms.counts, *gt, n=n)  # the repeated canvases of a short batch stay out
             sl.out_host.copy_(block, non_blocking=True)  # packed NMS outputs + tp words: one D2H copy
             sl.done.record()
         tcls = cls.numpy()
@@ -239,10 +309,15 @@ class Validator:
         self._collect_through(None)
 
     def stats(self) -> dict:
-        """`DetectionValidator.get_stats`: flush, compute, clear; returns `DetMetrics.results_dict`."""
+        """`DetectionValidator.get_stats`: flush, compute, clear; returns `DetMetrics.results_dict`.  The run's
+        confusion matrix is left in `self.confusion_matrix` and the device tables are cleared with the statistics."""
         self.flush()
         self.metrics.process()
         self.metrics.clear_stats()
+        self.confusion_matrix = ConfusionMatrix(self.cm_names, sum(c.numpy().astype(np.int64) for c in self.confusion))
+        for c in self.confusion:
+            c.zero_()
+        torch.cuda.synchronize(self.device)  # nothing is in flight here: the next run's slot streams see zeros
         return self.metrics.results_dict
 
     def close(self) -> None:

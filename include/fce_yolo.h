@@ -26,6 +26,7 @@
  *   fce_tta_merge         nn/tasks.py:446-484 _descale_pred, _clip_augmented (+ the torch.cat of :444)
  *   fce_val_match         models/yolo/detect/val.py:274-288 _process_batch: utils/metrics.py:57-77 box_iou +
  *                         engine/validator.py:266-306 BaseValidator.match_predictions
+ *   fce_val_confusion     utils/metrics.py:441-518 ConfusionMatrix.process_batch
  *   fce_copy              the NCHW <-> NHWC / fp32 <-> fp16 edges a drop-in module needs
  *   fce_net_*             nn/tasks.py:160-188 BaseModel._predict_once (graph executor) and
  *                         nn/autobackend.py:667-700 / :912-926 (forward, warmup) in hipGraph form
@@ -351,6 +352,25 @@ size_t fce_val_match_workspace_bytes(int n, int max_det, int max_gt_total, int n
 int fce_val_match(const float* dets, const int32_t* counts, int n, int max_det, const float* gt_boxes,
                   const float* gt_cls, const int32_t* gt_off, const float* iouv, int niou, void* ws, size_t ws_bytes,
                   uint16_t* tp, void* stream);
+
+/* utils/metrics.py:441-518 ConfusionMatrix.process_batch (called per image from models/yolo/detect/val.py
+ * update_metrics when plots is on, the default), for a whole batch in one launch, one workgroup per image, ADDED into
+ * matrix (nc + 1, nc + 1) int32, row = predicted class, column = true class, index nc = background; the caller
+ * zeroes it before a run.  Inputs as fce_val_match; only images 0..n-1 are read.  Per image: detections with
+ * conf > conf_thres take part; iou = box_iou(gt, det), not masked by class; a detection claims its best GT when that
+ * IoU > iou_thres; of a GT's claimants the one with the largest IoU keeps it: matrix[cls(det), cls(gt)] += 1; every
+ * other GT: matrix[nc, cls(gt)] += 1; every other participating detection: matrix[cls(det), nc] += 1.  Exactly equal
+ * IoUs (undefined in the reference: numpy's unstable sort) go to the higher GT index and the higher detection index,
+ * numpy's result for up to 16 candidate pairs.  conf is the threshold itself: the reference's replacement of None and
+ * 0.001 by 0.25 is the caller's.  Classes are the fp32 values truncated (.int()).  The class values are device data
+ * that no host entry can see without a synchronisation: a class outside 0..nc-1 adds nothing to the matrix and one to
+ * the int32 error word at the head of the workspace, which the caller zeroes with the matrix and reads with it.
+ * The workspace is 16 bytes up to 512 detections per image and 8 bytes per detection slot more beyond.  Nothing is
+ * allocated, nothing synchronises and the launch reads no descriptor memory: capturable like fce_val_match. */
+size_t fce_val_confusion_workspace_bytes(int n, int max_det);
+int fce_val_confusion(const float* dets, const int32_t* counts, int n, int max_det, const float* gt_boxes,
+                      const float* gt_cls, const int32_t* gt_off, int nc, float conf, float iou_thres, void* ws,
+                      size_t ws_bytes, int32_t* matrix, void* stream);
 
 /* ---------------------------------------------------------------- layout / dtype edges */
 /* dst = src with layout / dtype conversion (same n,c,h,w). */

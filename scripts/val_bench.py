@@ -9,8 +9,8 @@ matching has true positives).  Prints one JSON line with images/s of
   (b) pipeline      the same Pipeline (same lanes, same NMS) with no matching and no copy to the host;
   (c) host_match    (b) plus, per batch, the NMS outputs copied to the host and matched per image in numpy
                     (tests/val_ref.py: the reference's per-image loop without its per-image sync);
-and the device times of one fce_val_match and of one NMS at these settings per batch (events around back-to-back
-calls on a finished batch's data).
+and the device times of one fce_val_match, of one fce_val_confusion and of one NMS at these settings per batch (events
+around back-to-back calls on a finished batch's data).
 """
 
 from __future__ import annotations
@@ -121,6 +121,14 @@ def main():
         gt = V.pack_gt(labels[0]["batch_idx"], labels[0]["cls"], labels[0]["bboxes"], B, S, S)
         gb, gc, off = (t.to(dev) for t in gt)
         res["val_match_ms"] = timed(lambda: v.matcher(nms.dets, nms.counts, gb, gc, off), 200)
+        # the confusion matrix at the validator's threshold (0.25) and with every detection taking part (0.001)
+        cm = v.confusion[k]
+        res["val_confusion_ms"] = timed(lambda: cm(nms.dets, nms.counts, gb, gc, off), 200)
+        res["participating_per_image"] = float((nms.dets[:, :, 4] > cm.conf).sum().item()) / B
+        every = V.DeviceConfusionMatrix(eng.nc, B, 300, dev, conf=0.001)
+        res["val_confusion_all_detections_ms"] = timed(lambda: every(nms.dets, nms.counts, gb, gc, off), 200)
+        for c in v.confusion:
+            c.zero_()
         pred, best = v.pipe.preds[k], v.pipe.bests[k]
         res["nms_conf001_multilabel_ms"] = timed(lambda: nms(pred, best), 50)
         std = NMS(B, eng.anchors, eng.nc, dev)
