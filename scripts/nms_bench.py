@@ -1,10 +1,11 @@
 """Device NMS on the bench batch (n-fce 640 bs32 predictions of the seeded model): the one-workgroup kernel
-(default) against the multi-workgroup path (FCE_NMS_V2=1): bitwise-equal outputs, event-timed per call.
+(default) against the multi-workgroup path (FCE_NMS_V2=1): bitwise-equal outputs (a digest of the output buffer per path and key source), event-timed per call.
 
     python scripts/nms_bench.py [--batch 32] [--imgsz 640] [--iters 50]
 """
 
 import argparse
+import hashlib
 import os
 import sys
 from pathlib import Path
@@ -32,6 +33,10 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
+def digest(t):
+    return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()[:16]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -56,6 +61,9 @@ def main():
         nms(pred, best)
         torch.cuda.synchronize()
         out = nms.buf.clone()
+        nms(pred)
+        torch.cuda.synchronize()
+        print(f"{mode}: nms.buf sha256 with keys {digest(out)}, with its own arg-max {digest(nms.buf)}", flush=True)
         t_keys = timed(lambda: nms(pred, best), a.iters)
         t_plain = timed(lambda: nms(pred), a.iters)
         res[mode] = out

@@ -1111,6 +1111,53 @@ def test_nms_top_selection_and_class_buckets(case, device, nms_path):
             assert np.array_equal(dets[b].cpu().numpy(), od[b]), (case, iou, max_det, b)
 
 
+def _degenerate_case():
+    """B=2, A=192, nc=2, six clusters; image 0 also holds zero-width, zero-height, negative-width and overflowing
+    boxes, image 1 stays clean.  Returns the prediction and the anchors of image 0's degenerate boxes."""
+    rng = np.random.default_rng(0)
+    B, A, nc = 2, 192, 2
+    p = np.zeros((B, 4 + nc, A), np.float32)
+    for b in range(B):
+        centres = rng.uniform(40, 240, (6, 2))
+        k = rng.integers(0, 6, A)
+        p[b, 0:2] = (centres[k] + rng.normal(0, 4, (A, 2))).T
+        p[b, 2:4] = rng.uniform(30, 50, (2, A))
+        p[b, 4 + rng.integers(0, nc, A), np.arange(A)] = rng.uniform(0.3, 0.99, A).astype(np.float32)
+    bad = rng.permutation(A)[:40]
+    p[0, 2, bad[0:12]] = 0.0     # w = 0
+    p[0, 3, bad[12:24]] = 0.0    # h = 0
+    p[0, 2, bad[24:36]] = -25.0  # w < 0
+    p[0, 2:4, bad[36:40]] = 3e19  # area overflows to inf, IoU NaN
+    p[0, 4:, bad[36:40]] = 0.0
+    p[0, 4, bad[36:40]] = np.float32([0.99, 0.98, 0.97, 0.96])
+    return p, bad
+
+
+@pytest.mark.parametrize("max_det", [300, 5])
+def test_nms_degenerate_boxes_literal_path(max_det, device, nms_path):
+    """Boxes with area <= 0 or a non-finite area take the literal per-box greedy (the reference's loop with its
+    `no overlap -> keep all` early exit and NaN IoUs dropped); max_det 5 stops inside that loop.  Image 1 has no
+    such box, so one launch runs the literal loop in one workgroup and the tiled greedy in the other.  Kept
+    indices and rows bit-exact vs the oracle."""
+    p, bad = _degenerate_case()
+    with np.errstate(over="ignore", invalid="ignore"):
+        xyxy = nms_oracle.xywh2xyxy(p[0, :4].T)
+        area = (xyxy[:, 2] - xyxy[:, 0]) * (xyxy[:, 3] - xyxy[:, 1])
+        clean = nms_oracle.xywh2xyxy(p[1, :4].T)
+        od, ok = nms_oracle.non_max_suppression(p, 0.25, 0.7, max_det=300)
+        odm, okm = nms_oracle.non_max_suppression(p, 0.25, 0.7, max_det=max_det)
+    assert (area[bad[:36]] <= 0).all() and (area[bad[:24]] == 0).any() and (area[bad[24:36]] < 0).all()
+    assert not np.isfinite(area[bad[36:]]).any()
+    assert ((clean[:, 2] - clean[:, 0]) * (clean[:, 3] - clean[:, 1]) > 0).all()
+    ncand = (p[:, 4:].max(1) > 0.25).sum(1)
+    assert (ncand == 192).all() and all(0 < len(ok[b]) < ncand[b] for b in range(2))  # suppression happened
+    dets, keep = non_max_suppression(torch.from_numpy(p).to(device), 0.25, 0.7, max_det, return_idxs=True)
+    for b in range(2):
+        assert len(okm[b]) == min(max_det, len(ok[b]))
+        assert np.array_equal(keep[b].cpu().numpy(), okm[b]), (b, max_det)
+        assert np.array_equal(dets[b].cpu().numpy(), odm[b]), (b, max_det)
+
+
 def test_fused_best_class_keys_match_pred_and_nms(device):
     """The cls epilogue's per-anchor best-class keys (atomic max, box epilogue zeroes) equal torch.max over
     the pred rows (first maximum), and the NMS fed with them equals the NMS that does its own arg-max."""
